@@ -1,7 +1,12 @@
-"""bench.py -- BASELINE.json's metric on its configs[1] workload, plus one block per other BASELINE config.
+"""bench.py -- BASELINE.json's metric on its configs[1] workload; with --full, plus one block per other BASELINE config.
 
     python bench.py --gpus N --steps K --warmup W        (N > 1 launches itself: one process per GPU over RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line: the contract keys, `config`, `roofline` (HIP events inside
+the timed region) and a `summary` of the headline alone.  `--dump-outputs DIR` also writes what the last timed step computed
+(DIR/exp.npy, DIR/log.npy; inputs are seeded, so two builds can be compared output for output).  `--full` adds everything below
+that is not the headline: "cpu_baseline", the block per other config, the sharded legs, the side file of full blocks.
 
 Workload ("se3_explog_b10m"): batched SE3 Exp -> Log forward, B = 10,000,000 rows of fp32 per GPU
 (BASELINE.json configs[1]; inputs `pp.randn_se3(B)`, seed = rank), through the public API
@@ -1150,20 +1155,53 @@ def _finish(out):
     _emit_line(_compact(out, path))
 
 
+DUMP_BYTES = 60_000_000         # --dump-outputs: all files of all ranks together stay below this
+
+
+def _dump_outputs(d, rank, world, arrays):
+    """--dump-outputs DIR: the arrays the last timed step handed back, as DIR/<name>.npy (DIR/<name>_rank<r>.npy with more than
+    one rank), float32 or float64.  All arrays have one row per input row; when they exceed DUMP_BYTES the same sorted sample of
+    rows (numpy default_rng(0), so the same rows in every run with the same arguments) is kept of each."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    ts = {}
+    for name, v in arrays.items():
+        t = (v.tensor() if hasattr(v, "tensor") else v).detach()
+        ts[name] = t if t.dtype in (torch.float32, torch.float64) else t.to(torch.float32)
+    rows = next(iter(ts.values())).shape[0]
+    row_bytes = sum(t[0].numel() * t.element_size() for t in ts.values())
+    keep = min(rows, DUMP_BYTES // (world * row_bytes))
+    idx = None
+    if keep < rows:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(rows, keep, replace=False)))
+    for name, t in ts.items():
+        part = t if idx is None else t[idx.to(t.device)]
+        np.save(os.path.join(d, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), part.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--rows", type=int, default=10_000_000, help="rows per GPU (BASELINE configs[1]: 10M)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only (clean rocprof kernel statistics)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else: the legs of the other BASELINE configs, the CPU baselines, "
+                         "with N > 1 the sharded legs; writes the side file of full blocks.  Off: headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (X = x.Exp(), y = X.Log(); a fixed seeded "
+                         "sample of rows when larger than the budget) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave the other legs out")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + --standin: CPU dry run of the multi-process plumbing (tests/test_bench_launch.py)")
     ap.add_argument("--standin", action="store_true",
                     help="TEST ONLY: run on CPU tensors with the oracle stand-in of the HIP library (tests/oracle_backend.py); "
                          "nothing it prints is a measurement")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         _self_launch(a)
     _claim_stdout()
@@ -1247,6 +1285,8 @@ def main():
     if launched:
         dist.all_reduce(seen)
     ranks_seen = int(seen.item())
+    if a.dump_outputs:
+        _dump_outputs(a.dump_outputs, rank, world, {"exp": X, "log": y})
 
     out = None
     if rank == 0:
@@ -1284,8 +1324,8 @@ def main():
     gc.freeze()                   # (a gen-2 collection with torch loaded is a 40-70 ms pause)
     small = standin                # the dry run shrinks every leg: it checks plumbing, not speed
     instances = {}
-    if world == 1 and not a.no_secondary and rank == 0:
-        x = y = X = None                       # (the headline's 0.8 GB go back to the allocator before the 10 M-row legs)
+    if world == 1 and a.full and not a.no_secondary and rank == 0:
+        x = y = X = None                      # (the headline's 0.8 GB go back to the allocator before the 10 M-row legs)
         def make_instances():
             # (after the latency-sensitive legs: building the host instances runs multi-threaded CPU kernels whose worker
             #  threads keep spinning for a while and would sit in c1's microseconds)
@@ -1313,7 +1353,7 @@ def main():
                     out[key] = res
             except Exception as e:    # never lose the headline line over a secondary figure
                 out[key] = {"error": repr(e)}
-    if world == 1 and not a.no_cpu_baseline and rank == 0 and not standin:
+    if world == 1 and a.full and not a.no_cpu_baseline and rank == 0 and not standin:
         out["cpu_baseline"] = cpu_baseline()
         if not a.no_secondary:
             try:
@@ -1324,13 +1364,13 @@ def main():
             for key, blk in per_leg.items():
                 if isinstance(out.get(key), dict):
                     out[key]["cpu_baseline"] = blk
-    if world == 1 and standin and rank == 0:
+    if world == 1 and a.full and standin and rank == 0:
         dt, _ = _cpu_worker((0, 20_000))           # the block's shape in the dry run (one process, 20k rows of the numpy port)
         out["cpu_baseline"] = {"value": 20_000 / dt, "unit": "SE3 Exp+Log pairs/s", "cores": 1, "kind": "port",
                                "sample": "DRY RUN: 20000 rows of oracle/lie_np.py se3_exp_fwd+se3_log_fwd in this process"}
     if rank == 0 and out is not None:
         _lift_second_half(out)
-    sharded = launched and not a.no_secondary and (world > 1 or os.environ.get("PPLIE_BENCH_SHARDED") == "1")
+    sharded = a.full and launched and not a.no_secondary and (world > 1 or os.environ.get("PPLIE_BENCH_SHARDED") == "1")
     if sharded:
         # every rank takes part; a watchdog keeps the headline line if a collective wedges (nothing in the timed
         # region above depends on this)
@@ -1425,8 +1465,10 @@ def main():
                         f.write(txt + "\n")
                 except OSError:
                     pass
-    elif rank == 0:
+    elif rank == 0 and a.full:
         _finish(out)
+    elif rank == 0:
+        _emit_line(_compact(out, None))         # headline only: the line is the whole record, no side file
     if launched:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -11,7 +11,7 @@
   parametrising r0 <- Exp(eps) r0 at eps = 0 and by pairing the rotation cotangent with the first-order log of
   rot_f * stopgrad(rot_f)^-1.
 
-Pinned against tests/golden/grad_golden.npz (gradients recorded from the real reference by tests/golden/make_grad_golden.py)
+Pinned against tests/golden/grad_golden*.npz (gradients recorded from the real reference by tests/golden/make_grad_golden.py)
 in tests/test_grad_oracle_host.py.  Nothing under pypose_amd/ imports this."""
 import numpy as np
 import torch

@@ -1,4 +1,4 @@
-"""tests/golden/grad_golden.npz: GRADIENTS through the reference's product scans and through its IMUPreintegrator, recorded
+"""tests/golden/grad_golden.npz + grad_golden_long_imu.npz (two files: each stays below 1 MiB): GRADIENTS through the reference's product scans and through its IMUPreintegrator, recorded
 from the REAL reference (build container only):
     PYTHONDONTWRITEBYTECODE=1 PYTHONPATH=/root/reference python tests/golden/make_grad_golden.py
 (the reference differentiates log2(L) Hillis-Steele rounds, basics/ops.py:27-36, and the composed IMU graph,
@@ -93,5 +93,8 @@ loss = torch.nn.functional.mse_loss(o["pos"], gt_pos) + 5e2 * (rotk * o["rot"].I
 loss.backward()
 S["imu/example/loss"] = loss.detach().numpy()
 S["imu/example/g_gyro"], S["imu/example/g_acc"] = gyro.grad.numpy(), acc.grad.numpy()
-np.savez_compressed(OUT, **S)
-print("wrote", OUT, len(S), os.path.getsize(OUT))
+OUT2 = OUT.replace(".npz", "_long_imu.npz")          # the long trajectory and the IMU cases
+S2 = {k: v for k, v in S.items() if k.startswith(("imu/", "scan/SE3/long/"))}
+np.savez_compressed(OUT, **{k: v for k, v in S.items() if k not in S2})
+np.savez_compressed(OUT2, **S2)
+print("wrote", OUT, len(S) - len(S2), os.path.getsize(OUT), OUT2, len(S2), os.path.getsize(OUT2))

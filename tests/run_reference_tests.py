@@ -1,6 +1,6 @@
 """Run the REFERENCE's own pytest files against this package, imported under the name ``pypose``.
 
-    python tests/run_reference_tests.py [--cpu-oracle] /root/reference/tests/lietensor/test_lietensor.py ...
+    python tests/run_reference_tests.py [--cpu-oracle] oracle/_ref/tests/lietensor/test_lietensor.py ...
 
 This is the drop-in check of SURVEY.md section 8(b): the files are executed where they lie (nothing is copied) with
 ``sys.modules["pypose"]`` pointing at ``pypose_amd``.  On a GPU box the kernels run (the files pick ``cuda`` when it is
@@ -65,8 +65,12 @@ def main(argv):
     if default_cuda:
         # every factory call of the test files (torch.randn, pp.randn_SE3, nn.Module parameters ...) lands on the MI355X
         torch.set_default_device("cuda")
+    # collection walks down from the confcutdir to each file and lists every directory on the way: cut at the files' own
+    # tree, so that no directory above it has to be listable by this user
+    dirs = [os.path.dirname(os.path.abspath(a.split("::")[0])) for a in argv if not a.startswith("-")]
+    cut = [f"--confcutdir={os.path.commonpath(dirs)}"] if dirs else []
     with ctx:
-        rc = int(pytest.main(["-q", "-p", "no:cacheprovider", "--rootdir=/tmp", "-rf", *argv]))
+        rc = int(pytest.main(["-q", "-p", "no:cacheprovider", "--rootdir=/tmp", *cut, "-rf", *argv]))
     if os.environ.get("PPLIE_REPORT_LIBS"):
         # evidence for the caller that the kernels -- not a stand-in -- did the arithmetic
         with open("/proc/self/maps") as f:

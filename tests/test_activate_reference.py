@@ -1,5 +1,5 @@
 """The activation shim (pypose_amd.activate) on top of the REAL reference, when it is present
-(build container only: /root/reference does not exist on the GPU box).  With the oracle stand-in
+(oracle/_ref, the copy that build() makes through oracle/Makefile).  With the oracle stand-in
 backend and force=True every Lie op of ``pypose`` runs through pypose_amd's Functions; results
 and gradients must coincide with the reference's own, and the reference's LM must walk the same
 trajectory."""
@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-REF = "/root/reference"
+REF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
 pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "pypose")), reason="reference not present")
 
 

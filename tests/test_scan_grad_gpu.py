@@ -1,5 +1,5 @@
 """Row a19 / a28 with gradients: the one-pass backward kernels (pplie_scan_<g>_bwd, pplie_imu_integrate_bwd) against gradients
-recorded from the REAL reference (tests/golden/grad_golden.npz), against the sequential oracle at larger sizes, and against the
+recorded from the REAL reference (tests/golden/grad_golden.npz, grad_golden_long_imu.npz), against the sequential oracle at larger sizes, and against the
 composed route (the reference's Hillis-Steele formulation on the HIP Mul kernels) at BASELINE configs[4]'s shape."""
 import os
 
@@ -13,7 +13,8 @@ from pypose_amd.basics import scan as scan_mod
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-G = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "grad_golden.npz")))
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+G = {k: v for f in ("grad_golden.npz", "grad_golden_long_imu.npz") for k, v in np.load(os.path.join(_GOLDEN, f)).items()}
 CTOR = {"SO3": pp.SO3, "SE3": pp.SE3, "Sim3": pp.Sim3, "RxSO3": pp.RxSO3}
 KEY = {"SO3": "so3", "SE3": "se3", "Sim3": "sim3", "RxSO3": "rxso3"}
 DIMS = {"a": 1, "b": 0, "c": 1, "d": 1, "e": 1, "f": 0, "long": 1}

@@ -6,7 +6,7 @@ bash tools/gpu_visit.sh $TAG tests smoke bench prof
 cp "$O/bench_line.json" "$O/bench_final.json"
 f=$(find "$O/prof" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$O/prof_headline_kernel_stats.csv"
 # all-legs kernel statistics
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_all" -o all -- python "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline > "$O/rocprof_all.log" 2>&1)
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_all" -o all -- python "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline > "$O/rocprof_all.log" 2>&1)
 f=$(find "$O/prof_all" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$O/prof_all_kernel_stats.csv"
 find "$O/prof_all" "$O/prof" -name "*kernel_trace.csv" -delete 2>/dev/null; find "$O" -name "*.db" -delete 2>/dev/null
 for leg in lm_pgo lm_pgo_100k lm_invnet; do bash tools/gpu_prof_leg.sh $TAG $leg > /dev/null 2>&1; ls "$O/${leg}_kernel_stats.csv" 2>/dev/null; done
