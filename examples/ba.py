@@ -18,13 +18,16 @@ from pypose_amd.autograd.function import psjac
 
 
 class Reproj(nn.Module):
-    def __init__(self, K, C, P):
+    def __init__(self, K, C, P, closed_form=True):
         super().__init__()
+        self.closed_form = closed_form
         self.K = pp.Parameter(K, sjac=True)
         self.C = pp.Parameter(C, sjac=True)
         self.P = pp.Parameter(P, sjac=True)
 
     def forward(self, observe, cidx, pidx):
+        if self.closed_form:      # one kernel: residual + closed-form blocks for K, C and P (csrc/bal.hip)
+            return pp.bal_reprojerr(self.P[pidx], observe, self.K[cidx], self.C[cidx])
         return Reproj.project(self.K[cidx], self.C[cidx], self.P[pidx]) - observe
 
     @psjac
@@ -63,9 +66,12 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--solver", choices=["pcg", "cholesky"], default="pcg",
                     help="pcg: matrix-free PCG on the full system (the reference example); cholesky: exact Schur-complement solve")
+    ap.add_argument("--closed-form", action=argparse.BooleanOptionalAction, default=True,
+                    help="project with pp.bal_reprojerr (closed-form Jacobian blocks); --no-closed-form: the hand-written formula, "
+                         "linearised by autograd sweeps")
     a = ap.parse_args(argv)
     args, (K0, C0, P0) = synthetic(a.cameras, a.points, a.per_point, a.device)
-    model = Reproj(K0, C0, P0)
+    model = Reproj(K0, C0, P0, a.closed_form)
     solver = pp.optim.solver.PCG(tol=1e-4, maxiter=250) if a.solver == "pcg" else pp.optim.solver.Cholesky()
     optimizer = pp.optim.LM(model, solver=solver, strategy=pp.optim.strategy.TrustRegion(radius=1e4), reject=30, sparse=True)
     loss0 = float(optimizer.model.loss(args, None).detach())
@@ -74,7 +80,8 @@ def main(argv=None):
         loss = optimizer.step(args)
     torch.cuda.synchronize()
     print(f"{a.cameras} cameras, {a.points} points, {args[0].shape[0]} observations: loss {loss0:.6g} -> {float(loss):.6g} in "
-          f"{a.steps} LM steps, {(time.perf_counter() - t0) / a.steps * 1e3:.1f} ms/step on the '{optimizer.linearization}' path")
+          f"{a.steps} LM steps, {(time.perf_counter() - t0) / a.steps * 1e3:.1f} ms/step on the '{optimizer.linearization}' path, "
+          f"{optimizer._last_blocks} blocks")
     return loss0, float(loss)
 
 

@@ -39,6 +39,10 @@ CFLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"
 # is compiled with correctly rounded fp32 division / square root and without -fapprox-func (e.g. a future kernel whose fp64
 # helpers or whose parity needs the last ulp).  No file of this tree asks for it today: parity is green with the fast forms.
 _FAST = ("-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fapprox-func")
+# Per-file opt-out of the packed fp32 instructions (v_pk_add / mul / fma_f32), the same way:
+#     // pplie-build: no-packed-fp32
+# -fno-slp-vectorize already keeps the vectoriser from forming them; this takes the instructions away from the back end too.
+_NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 def _flags_for(src: Path):
@@ -46,9 +50,12 @@ def _flags_for(src: Path):
         head = "".join(src.open().readlines()[:20])
     except OSError:
         head = ""
+    flags = CFLAGS
     if "pplie-build: precise" in head:
-        return [f for f in CFLAGS if f not in _FAST]
-    return CFLAGS
+        flags = [f for f in flags if f not in _FAST]
+    if "pplie-build: no-packed-fp32" in head:
+        flags = flags + _NO_PK
+    return flags
 
 
 def _sources():

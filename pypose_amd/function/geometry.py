@@ -7,9 +7,16 @@ messages.  With extrinsics, ``point2pixel`` / ``reprojerr`` are ONE kernel per d
 the backward ``pplie_reproj_vjp`` contracts them -- and the LM optimizers take the blocks as they are instead of
 sweeping the autograd graph (``closed_form_blocks`` below, optim/multigraph.py).  Without extrinsics the pinhole
 algebra is plain tensor arithmetic on whatever device the inputs live on.
+
+``bal_point2pixel`` / ``bal_reprojerr`` are the Snavely / BAL model of the reference's bundle-adjustment example (focal length
+and two radial distortion coefficients per camera) the same way (csrc/bal.hip): ``pplie_se3_bal_lin`` returns the residual and
+the blocks for intrinsics, pose and point, ``pplie_bal_vjp`` contracts all three.
 """
+import ctypes
+
 import torch
 
+from .. import _C
 from ..lietensor import LieTensor
 from ..lietensor import operation as _op
 
@@ -75,6 +82,166 @@ def _reproject(points, intrinsics, extrinsics, pixels):
     return r
 
 
+# ---- Snavely / BAL model (csrc/bal.hip): four operands in, three gradients out -- entry points with explicit pointer
+# arguments, launched from here (the uniform row launcher _C.row_op carries 3 inputs and 2 outputs)
+_BAL_FWD_SIG = [ctypes.c_void_p] * 5 + [ctypes.c_int64, ctypes.c_void_p]
+_BAL_LIN_SIG = [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_void_p]
+_BAL_VJP_SIG = [ctypes.c_void_p] * 5 + [ctypes.c_int64, ctypes.c_void_p]
+
+
+def _bal_call(name, sig, ins, in_widths, out_widths):
+    """``pplie_<name>_{f32,f64}`` on contiguous ``[n, w]`` device tensors (a ``None`` input is a NULL pointer); returns the
+    freshly allocated outputs"""
+    x0 = ins[0]
+    n = x0.shape[0]
+    for t, w in zip(ins, in_widths):
+        if t is not None and (t.dim() != 2 or t.shape != (n, w) or t.dtype != x0.dtype or t.device != x0.device
+                              or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f"pypose_amd: {name}: inputs must be contiguous [N,W] device tensors of one dtype")
+    if x0.dtype not in _C._SUFFIX:
+        raise TypeError(f"pypose_amd: {name} supports float32/float64, got {x0.dtype}")
+    outs = tuple(torch.empty((n, w), dtype=x0.dtype, device=x0.device) for w in out_widths)
+    if n:
+        sym = "pplie_" + name + _C._SUFFIX[x0.dtype]
+        fn = _C.library().symbol(sym, sig)
+        with _C._on_device(x0.device):
+            code = fn(*[None if t is None else t.data_ptr() for t in ins], *[o.data_ptr() for o in outs], n, _C.stream_ptr(x0.device))
+        _C.check(code, sym)
+    return outs
+
+
+def _bal_fwd(K, X, p, uv=None):
+    return _bal_call("se3_bal_fwd", _BAL_FWD_SIG, (K, X, p, uv), (3, 7, 3, 2), (2,))[0]
+
+
+def _bal_lin(K, X, p, uv=None):
+    return _bal_call("se3_bal_lin", _BAL_LIN_SIG, (K, X, p, uv), (3, 7, 3, 2), (2, 24))
+
+
+def _bal_vjp(J, g):
+    return _bal_call("bal_vjp", _BAL_VJP_SIG, (J, g), (24, 2), (3, 7, 3))
+
+
+def _bal_rows(t, lead, w):
+    """``t`` broadcast to ``lead + (w,)`` as contiguous rows; an already contiguous operand of that shape is not copied"""
+    if t is None:
+        return None
+    if t.shape[:-1] != lead:
+        t = t.expand(lead + (w,))
+    return t.reshape(-1, w).contiguous()
+
+
+def _bal_composed(K, X, p, uv):
+    """the model from the differentiable ops (SE3 Act + tensor arithmetic): host tensors, other dtypes, a stand-in back end,
+    and the backward of the backward"""
+    from ..lietensor import lietensor as lt
+    q = (X if isinstance(X, LieTensor) else lt._wrap(X, lt.SE3_type)).Act(p)
+    n = -q[..., :2] / q[..., 2:3]
+    rho = n.square().sum(dim=-1, keepdim=True)
+    u = K[..., :1] * (1 + K[..., 1:2] * rho + K[..., 2:3] * rho.square()) * n
+    return u if uv is None else u - uv
+
+
+class _BalVjp(torch.autograd.Function):
+    """(gK, gX, gp) = g J in one launch (``pplie_bal_vjp``); J [..., 24] is shared by every slice of a batched cotangent"""
+
+    @staticmethod
+    def forward(J, g):
+        if _op._is_legacy_batched(g):
+            # jacobian(vectorize=True) / the optimizers' block sweeps: the legacy vmap does not consult Function.vmap
+            lvl = _op._legacy_level(g)
+            gb = torch._remove_batch_dim(g, lvl, 1, 0)
+            outs = [_BalVjp.forward(J, gb[b]) for b in range(gb.shape[0])]
+            return tuple(torch._add_batch_dim(torch.stack([o[k] for o in outs]), 0, lvl) for k in range(3))
+        lead = J.shape[:-1]
+        outs = _bal_vjp(J.reshape(-1, 24), _bal_rows(g, lead, 2))
+        return tuple(o.view(lead + (w,)) for o, w in zip(outs, (3, 7, 3)))
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError("BalVjp: a recorded backward takes the composed route (_BalReproj.backward)")
+
+    @staticmethod
+    def vmap(info, in_dims, J, g):
+        J, g = _op._fold_vmap(in_dims, (J, g))
+        return _BalVjp.apply(J.contiguous(), g), (0, 0, 0)
+
+
+class _BalReproj(torch.autograd.Function):
+    """r = f (1 + k1 |n|^2 + k2 |n|^4) n - uv, n = -q_xy / q_z, q = X . p, for broadcastable (K [...,3], pose [...,7],
+    point [...,3], uv [...,2] or None); saves J [...,24] = 2 x [dK | dpose | dpoint]."""
+
+    @staticmethod
+    def forward(K, X, p, uv):
+        lead = torch.broadcast_shapes(*[t.shape[:-1] for t in (K, X, p, uv) if t is not None])
+        r, J = _bal_lin(_bal_rows(K, lead, 3), _bal_rows(X, lead, 7), _bal_rows(p, lead, 3), _bal_rows(uv, lead, 2))
+        return r.view(lead + (2,)), J.view(lead + (24,))
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.save_for_backward(output[1], *[t for t in inputs if t is not None])
+        ctx.mark_non_differentiable(output[1])
+        ctx.has_uv = inputs[3] is not None
+        ctx.shapes = [None if t is None else tuple(t.shape) for t in inputs]
+
+    @staticmethod
+    def backward(ctx, g, _gJ):
+        J, K, X, p, *uv = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            # the backward itself is being recorded (create_graph=True): the same gradients from differentiable ops
+            ins = [t if t.requires_grad else t.detach().requires_grad_(True) for t in (K, X, p, *uv)]
+            out = _bal_composed(ins[0], ins[1], ins[2], ins[3] if uv else None)
+            grads = list(torch.autograd.grad([out], ins, [g.expand_as(out)], create_graph=True, allow_unused=True))
+            if not uv:
+                grads.append(None)
+        else:
+            gK, gX, gp = _BalVjp.apply(J, g)
+            grads = [gK, gX, gp, -g if ctx.has_uv and ctx.needs_input_grad[3] else None]
+        out = []
+        for grad, shape in zip(grads, ctx.shapes):
+            out.append(None if grad is None or shape is None else grad.sum_to_size(shape) if tuple(grad.shape) != shape else grad)
+        return tuple(out)
+
+    @staticmethod
+    def vmap(info, in_dims, K, X, p, uv):
+        if uv is None:
+            K, X, p = _op._fold_vmap(in_dims[:3], (K, X, p))
+        else:
+            K, X, p, uv = _op._fold_vmap(in_dims, (K, X, p, uv))
+        return _BalReproj.apply(K, X, p, uv), (0, 0)
+
+
+def _bal_on_kernels(*tensors):
+    t0 = tensors[0]
+    return _C._test_backend is None and all(t.is_cuda and t.dtype == t0.dtype for t in tensors) \
+        and t0.dtype in (torch.float32, torch.float64)
+
+
+def _bal_project(points, intrinsics, extrinsics, pixels):
+    """(..., 2) BAL residual (projection when ``pixels`` is None) through csrc/bal.hip; the closed-form blocks of all three
+    operands are offered to an active optimizer trace"""
+    present = [t for t in (intrinsics, extrinsics, points, pixels) if t is not None]
+    if not _bal_on_kernels(*present):
+        return _bal_composed(intrinsics, extrinsics, points, pixels)
+    X = extrinsics.tensor()
+    if not _closed_recorders and not (torch.is_grad_enabled() and any(t.requires_grad for t in present)) \
+            and not torch._C._are_functorch_transforms_active():
+        lead = torch.broadcast_shapes(*[t.shape[:-1] for t in present])
+        r = _bal_fwd(_bal_rows(intrinsics, lead, 3), _bal_rows(X, lead, 7), _bal_rows(points, lead, 3), _bal_rows(pixels, lead, 2))
+        return r.view(lead + (2,))
+    r, J = _BalReproj.apply(intrinsics, X, points, pixels)
+    if _closed_recorders:
+        Jm = J.reshape(J.shape[:-1] + (2, 12))
+        for rec in _closed_recorders:
+            rec.note_closed(r, [(intrinsics, Jm[..., 0:3]), (extrinsics, Jm[..., 3:9]), (points, Jm[..., 9:12])],
+                            blockers=[pixels] if pixels is not None and pixels.requires_grad else [])
+    return r
+
+
 def _need(cond, msg):
     assert cond, msg
 
@@ -136,6 +303,36 @@ def reprojerr(points, pixels, intrinsics, extrinsics=None, reduction='none'):
         err = _reproject(points, intrinsics, extrinsics, pixels)
     else:
         err = point2pixel(points, intrinsics) - pixels
+    return {'none': lambda e: e, 'norm': lambda e: e.norm(dim=-1), 'sum': lambda e: e.sum(dim=-1)}[reduction](err)
+
+
+def _bal_check(points, intrinsics, extrinsics, pixels=None):
+    _need(points.size(-1) == 3, "Points shape incorrect")
+    _need(intrinsics.size(-1) == 3, "Intrinsics shape incorrect.")
+    _need(isinstance(extrinsics, LieTensor) and extrinsics.shape[-1] == 7, "Type incorrect.")
+    lead = [points.shape[:-1], intrinsics.shape[:-1], extrinsics.shape[:-1]]
+    if pixels is not None:
+        _need(pixels.size(-1) == 2, "Shape not compatible.")
+        lead.append(pixels.shape[:-1])
+    torch.broadcast_shapes(*lead)                                      # raises on incompatible batch dims
+
+
+def bal_point2pixel(points, intrinsics, extrinsics):
+    """Pixels ``(*, 2)`` of ``points (*, 3)`` through the Snavely / BAL camera model: ``q = extrinsics . points``,
+    ``n = -q[:2] / q[2]``, ``u = f (1 + k1 |n|^2 + k2 |n|^4) n`` with ``intrinsics (*, 3) = (f, k1, k2)`` and ``extrinsics``
+    an SE3 ``(*, 7)``, world -> camera.  The leading dimensions broadcast.  One kernel on the device (csrc/bal.hip)."""
+    _bal_check(points, intrinsics, extrinsics)
+    return _bal_project(points, intrinsics, extrinsics, None)
+
+
+def bal_reprojerr(points, pixels, intrinsics, extrinsics, reduction='none'):
+    """:func:`bal_point2pixel` minus the observed ``pixels (*, 2)``: ``'none'`` -> ``(*, 2)``; ``'norm'`` / ``'sum'`` reduce
+    the last dim.  The kernel returns the residual together with its closed-form Jacobian blocks with respect to the
+    intrinsics, the pose and the point; the backward contracts them in one launch and the LM optimizers take them as they
+    are instead of sweeping the autograd graph."""
+    _bal_check(points, intrinsics, extrinsics, pixels)
+    _need(reduction in {'norm', 'sum', 'none'}, "Reduction method can only be 'norm'|'sum'|'none'.")
+    err = _bal_project(points, intrinsics, extrinsics, pixels)
     return {'none': lambda e: e, 'norm': lambda e: e.norm(dim=-1), 'sum': lambda e: e.sum(dim=-1)}[reduction](err)
 
 
