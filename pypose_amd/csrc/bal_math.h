@@ -12,7 +12,11 @@
 //   dr/dpoint row a = R^T m_a
 //
 // The division by q_z is the plain division of the model: the BAL model has no homo2cart, so there is no clamp of a depth
-// close to zero here (unlike se3_reproj_core); a zero depth gives inf / nan exactly as the composed torch formula does.
+// close to zero here (unlike se3_reproj_core).  A zero depth gives a non-finite residual and non-finite pose / point blocks
+// in that row and leaves every other row untouched; that is all that is guaranteed.  It is NOT the pattern of the composed
+// torch formula: with rho = inf the Horner form below is 1 + inf (k1 + k2 inf) = +-inf where 1 + k1 rho + k2 rho^2 is
+// inf - inf = nan for k1, k2 of opposite sign, and the device build's approximate fp64 reciprocal returns nan for 1 / 0
+// where IEEE division returns inf (tests/test_bal_host.py, tests/test_bal_edges_gpu.py).
 #pragma once
 #include "lie_math.h"
 

@@ -1,9 +1,10 @@
-// hostmath.cpp -- TEST INFRASTRUCTURE.  Compiles pypose_amd/csrc/lie_math.h (the exact per-row
+// hostmath.cpp -- TEST INFRASTRUCTURE.  Compiles pypose_amd/csrc/lie_math.h and bal_math.h (the exact per-row
 // arithmetic the HIP kernels run) with g++ so the arithmetic can be checked against the oracle
 // and the reference's golden vectors in the CPU-only build container.  Never loaded by the
-// product (pypose_amd has no CPU path); only tests/test_hostmath.py builds and loads it.
+// product (pypose_amd has no CPU path); only the tests build and load it (tests/hostmath_util.py).
 #include <stdint.h>
 #include "lie_math.h"
+#include "bal_math.h"
 
 using namespace pplie;
 
@@ -69,3 +70,26 @@ HM_1_1(k_so3_jr_fwd, so3_jr, 3, 9)
 HM_EXPORT(so3_jr_fwd, k_so3_jr_fwd)
 HM_2_1(k_so3_jr_bwd, so3_jr_bwd, 3, 9, 3)
 HM_EXPORT(so3_jr_bwd, k_so3_jr_bwd)
+
+// bal_math.h: four inputs in, so entry points of their own (tests/hostmath_util.py hostmath_bal_core / hostmath_bal_vjp).
+// uv == NULL: the projection; J == NULL: residual only
+template <class T> static void k_bal_core(const T* K, const T* X, const T* p, const T* uv, T* r, T* J, int64_t n) {
+  for (int64_t i = 0; i < n; ++i)
+    se3_bal_core<T>(K + i * 3, X + i * 7, p + i * 3, uv ? uv + i * 2 : nullptr, r + i * 2, J ? J + i * BAL_JROW : nullptr);
+}
+template <class T> static void k_bal_vjp(const T* J, const T* g, T* gK, T* gX, T* gp, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) bal_vjp<T>(J + i * BAL_JROW, g + i * 2, gK + i * 3, gX + i * 7, gp + i * 3);
+}
+extern "C" void hm_bal_core_f32(const float* K, const float* X, const float* p, const float* uv, float* r, float* J, int64_t n) {
+  k_bal_core<float>(K, X, p, uv, r, J, n);
+}
+extern "C" void hm_bal_core_f64(const double* K, const double* X, const double* p, const double* uv, double* r, double* J,
+                                int64_t n) {
+  k_bal_core<double>(K, X, p, uv, r, J, n);
+}
+extern "C" void hm_bal_vjp_f32(const float* J, const float* g, float* gK, float* gX, float* gp, int64_t n) {
+  k_bal_vjp<float>(J, g, gK, gX, gp, n);
+}
+extern "C" void hm_bal_vjp_f64(const double* J, const double* g, double* gK, double* gX, double* gp, int64_t n) {
+  k_bal_vjp<double>(J, g, gK, gX, gp, n);
+}
