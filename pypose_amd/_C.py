@@ -21,7 +21,8 @@ if os.environ.get("PPLIE_LIBRARY_FILE"):       # measurement tools only: an alte
     _LIB_PATH = _LIB_PATH.with_name(os.environ["PPLIE_LIBRARY_FILE"])
 
 _ERRORS = {-1: "bad argument (negative row count or null pointer)", -2: "kernel launch failed (hipGetLastError)",
-           -3: "the problem does not fit the device-resident variant (nothing launched)"}
+           -3: "the problem does not fit the device-resident variant (nothing launched)",
+           -4: "shape not supported by this kernel family (nothing launched)"}
 ECAPACITY = -3
 
 _ROW_SIG = [ctypes.c_void_p] * 5 + [ctypes.c_int64, ctypes.c_void_p]

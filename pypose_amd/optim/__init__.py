@@ -3,8 +3,9 @@ from .optimizer import GaussNewton
 from .optimizer import GaussNewton as GN
 from .optimizer import LevenbergMarquardt
 from .optimizer import LevenbergMarquardt as LM
-from .posegraph import PCG
+from .posegraph import PCG, SchurPCG
 solver.PCG = PCG
+solver.SchurPCG = SchurPCG
 
 
 def freeze_gc():

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import ctypes
 import warnings
+import weakref
 
 import torch
 
@@ -27,7 +28,7 @@ from .. import _C
 
 from ..lietensor import lietensor as _lt
 from . import blocks as _blocks
-from .posegraph import DENSE_LIMIT, PCG, _all_reduce
+from .posegraph import DENSE_LIMIT, PCG, SchurPCG, _all_reduce
 
 SCHUR_LIMIT = 12288        # largest reduced (non-eliminated) system assembled densely for the user's solver
 
@@ -314,7 +315,13 @@ class MultiGraphLinearization:
             # a direct solver was asked for and the problem is bipartite (bundle adjustment): eliminate the large,
             # mutually independent set of rows exactly and hand the small reduced system to the user's solver
             Dn = self._schur_solve(solver, shift, b)
+        elif isinstance(solver, SchurPCG) and self.schur_pcg_ops(shift, solver.precond, solver.check_every) is not None:
+            # PCG on the reduced system with the larger group eliminated, S applied implicitly (csrc/ba_schur.hip, or the
+            # tensor formulation of the same algebra); the stopping test is on the reduced residual
+            Dn = self.schur_pcg_ops(shift, solver.precond, solver.check_every).solve(solver)
+            self.opt._last_solve = "schur-pcg"
         else:
+            self.opt._last_solve = "pcg"
             if not isinstance(solver, PCG):
                 if not getattr(self.opt, '_warned_pcg', False):
                     warnings.warn(f"{type(solver).__name__} cannot factor a {tot}-unknown problem densely; "
@@ -344,15 +351,13 @@ class MultiGraphLinearization:
         return self.nodes_to_step(Dn)
 
     # -- Schur complement (bipartite problems) -----------------------------------------------------------
-    def schur_plan(self):
-        """Bipartite structure, or None.  Slots sharing one index vector form a group (BA: {K, C} by camera index, {P} by
-        point index); with exactly two groups, each parameter in one slot, the group with more rows is eliminated:
-        its rows couple only through the other group, so its block of the normal equations is block diagonal.  The
-        plan (cached on the optimizer per index structure) lists, for every pair of observations of the same
-        eliminated row, the two observation ids -- the fill of the reduced system."""
-        if hasattr(self, '_plan'):
-            return self._plan
-        self._plan = None
+    def bipartite_groups(self):
+        """Slots sharing one index vector form a group; with exactly two groups and each parameter in one slot the problem is
+        bipartite: ``a`` = the group with more rows (eliminated), ``b`` = the other (kept).  None otherwise.  Shared by the dense
+        Schur route (schur_plan) and the point-eliminated PCG (schur_pcg_ops)."""
+        if hasattr(self, '_groups'):
+            return self._groups
+        self._groups = None
         groups = []
         for k, (pi, idx, _) in enumerate(self.slots):
             for g in groups:
@@ -368,9 +373,24 @@ class MultiGraphLinearization:
         if any(self.N[self.slots[k][0]] != r for g, r in zip(groups, rows) for k in g[1]):
             return None
         a, b = (0, 1) if rows[0] >= rows[1] else (1, 0)
-        mb = sum(self.m[self.slots[k][0]] for k in groups[b][1])
-        if rows[b] * mb > SCHUR_LIMIT:
+        width = lambda g: sum(self.m[self.slots[k][0]] for k in groups[g][1])
+        self._groups = {"groups": groups, "ab": (a, b), "rows": rows, "a": groups[a][1], "b": groups[b][1], "Na": rows[a], "Nb": rows[b],
+                        "ia": groups[a][0], "ib": groups[b][0], "ma": width(a), "mb": width(b)}
+        return self._groups
+
+    def schur_plan(self):
+        """Bipartite structure, or None.  Slots sharing one index vector form a group (BA: {K, C} by camera index, {P} by
+        point index); with exactly two groups, each parameter in one slot, the group with more rows is eliminated:
+        its rows couple only through the other group, so its block of the normal equations is block diagonal.  The
+        plan (cached on the optimizer per index structure) lists, for every pair of observations of the same
+        eliminated row, the two observation ids -- the fill of the reduced system."""
+        if hasattr(self, '_plan'):
+            return self._plan
+        self._plan = None
+        G = self.bipartite_groups()
+        if G is None or G["Nb"] * G["mb"] > SCHUR_LIMIT:
             return None
+        groups, (a, b), rows = G["groups"], G["ab"], G["rows"]
         cache = self.opt.__dict__.setdefault('_schur_plans', {}) if hasattr(self.opt, '__dict__') else {}
         ia, ib = groups[a][0], groups[b][0]
         hit = cache.get((self.E, rows[a], rows[b]))
@@ -388,6 +408,30 @@ class MultiGraphLinearization:
             cache[(self.E, rows[a], rows[b])] = hit
         self._plan = {"a": groups[a][1], "b": groups[b][1], "Na": rows[a], "Nb": rows[b], **hit}
         return self._plan
+
+    def schur_pcg_ops(self, shift, precond="schur", check_every=8):
+        """The operators of the point-eliminated PCG for the current damping (S x, b_S, the preconditioner blocks, the
+        back-substitution), or None when the problem is not bipartite or carries a weight / a process group.  HIP kernels for
+        two-row residuals, an eliminated width of 3 and a kept width of 6 or 9 on a HIP device; the tensor formulation otherwise."""
+        G = self.bipartite_groups()
+        if G is None or self.W is not None or self.group is not None:
+            return None
+        key = (id(shift[0]), precond)
+        if getattr(self, '_schur_ops', (None,))[0] != key:
+            hip = (self.R.is_cuda and _C._test_backend is None and self.dr == 2 and G["ma"] == 3 and G["mb"] in (6, 9) and len(G["b"]) <= 3
+                   and len(G["a"]) == 1 and self.R.dtype in (torch.float32, torch.float64) and self.E < (1 << 31) // 24)
+            self._schur_ops = (key, _SchurHip(self, G, shift, precond, check_every) if hip else _SchurTensor(self, G, shift, precond), shift)
+        return self._schur_ops[1]
+
+    def _schur_split(self, xa, xb):
+        G, out = self._groups, [None] * len(self.params)
+        for x, ks in ((xa, G["a"]), (xb, G["b"])):
+            off = 0
+            for k in ks:
+                pi = self.slots[k][0]
+                out[pi] = x[:, off:off + self.m[pi]].contiguous()
+                off += self.m[pi]
+        return out
 
     def _schur_solve(self, solver, shift, b):
         P = self._plan
@@ -771,3 +815,238 @@ def try_multigraph_linearization(opt, pg, input, target, weight, R, params, rec,
     slots = [(k, ix, J) for (k, _), (ix, J) in sorted(slot_of.items())]
     opt._last_blocks = "closed-form" if closed else "autograd"
     return MultiGraphLinearization(opt, torch.cat(Ws) if weighted else None, torch.cat(Rs), params, slots)
+
+
+# -- point-eliminated PCG (SchurPCG) -----------------------------------------------------------------------------------
+# Observation form, with Jb_e [dr, mb] the kept group's concatenated blocks, Ja_e [dr, ma] the eliminated group's, b(e) / a(e) the
+# kept / eliminated row of observation e:  V_a = sum Ja^T Ja + diag(shift_a),  Pi t = t - Ja V^-1 Ja^T t,
+# S x = Jb^T Pi Jb x + shift_b o x,  b_S = -Jb^T Pi r,  x_a = -V^-1 sum Ja^T (r + Jb x_b).
+class _SchurTensor:
+    """the device-agnostic statement of the algebra (index_add_, batched products): host tensors, the stand-in back end,
+    shapes the kernels do not take"""
+
+    def __init__(self, lin, G, shift, precond):
+        self.lin, self.precond = lin, precond
+        cat = lambda ks: torch.cat([lin.slots[k][2] for k in ks], dim=-1)
+        cat_p = lambda ks: torch.cat([shift[lin.slots[k][0]] for k in ks], dim=-1)
+        self.Ja, self.Jb, self.ia, self.ib, self.Na, self.Nb = cat(G["a"]), cat(G["b"]), G["ia"], G["ib"], G["Na"], G["Nb"]
+        self.sa, self.sb = cat_p(G["a"]), cat_p(G["b"])
+        V = self._add(self.ia, self.Na, self._mm(self.Ja, self.Ja))
+        V.diagonal(dim1=-2, dim2=-1).add_(self.sa)
+        self.Vinv = torch.linalg.inv(V)
+
+    @staticmethod
+    def _mm(A, B):                                        # A^T B over the residual rows: [E, ., .]
+        return (A.unsqueeze(-1) * B.unsqueeze(-2)).sum(-3)
+
+    @staticmethod
+    def _add(idx, n, vals):
+        return torch.zeros((n,) + vals.shape[1:], dtype=vals.dtype, device=vals.device).index_add_(0, idx, vals)
+
+    def _proj(self, t):
+        s = self._add(self.ia, self.Na, (self.Ja * t.unsqueeze(-1)).sum(-2))
+        v = (self.Vinv * s.unsqueeze(-2)).sum(-1)
+        return t - (self.Ja * v[self.ia].unsqueeze(-2)).sum(-1)
+
+    def S(self, x):
+        u = self._proj((self.Jb * x[self.ib].unsqueeze(-2)).sum(-1))
+        return self._add(self.ib, self.Nb, (self.Jb * u.unsqueeze(-1)).sum(-2)) + self.sb * x
+
+    def b_S(self):
+        return -self._add(self.ib, self.Nb, (self.Jb * self._proj(self.lin.R).unsqueeze(-1)).sum(-2))
+
+    def blocks(self):
+        """(S_cc [Nb, mb, mb] -- precond "jacobi": the blocks of U + shift --, their inverses)"""
+        B = self._add(self.ib, self.Nb, self._mm(self.Jb, self.Jb))
+        B.diagonal(dim1=-2, dim2=-1).add_(self.sb)
+        if self.precond == "schur":                       # one coupling block per (kept row, eliminated row) pair
+            pair, inv = torch.unique(self.ib * self.Na + self.ia, return_inverse=True)
+            Gp = self._add(inv, pair.numel(), self._mm(self.Jb, self.Ja))
+            B.index_add_(0, pair // self.Na, -(Gp @ self.Vinv[pair % self.Na] @ Gp.mT))
+        return B, torch.linalg.inv(B)
+
+    def back(self, x):
+        t = self.lin.R + (self.Jb * x[self.ib].unsqueeze(-2)).sum(-1)
+        s = self._add(self.ia, self.Na, (self.Ja * t.unsqueeze(-1)).sum(-2))
+        return -(self.Vinv * s.unsqueeze(-2)).sum(-1)
+
+    def solve(self, solver):
+        Minv = self.blocks()[1]
+        shape = (self.Nb, self.Jb.shape[-1])
+        x = solver.solve(lambda v: self.S(v.view(shape)).reshape(-1), self.b_S().reshape(-1),
+                         lambda v: (Minv * v.view(shape).unsqueeze(-2)).sum(-1).reshape(-1)).view(shape)
+        return self.lin._schur_split(self.back(x), x)
+
+
+SCHUR_CCHUNK = 1024        # PPLIE_BA_SCHUR_CCHUNK: camera-major observations of one work item of pplie_ba_schur_cam
+_I, _P, _L = ctypes.c_int, ctypes.c_void_p, ctypes.c_int64
+_BS_PACK_SIG = [_I, _P, _P] + [_P] * 7 + [_L, _I, _I, _P]
+_BS_POINT_SIG = [_I, _I] + [_P] * 7 + [_I, _P, _I] + [_P] * 7 + [_I, _P]
+_BS_CAM_SIG = [_I, _P, _P, _P, _I] + [_P] * 11 + [_I, _I, _P]
+_BS_STEP_SIG = [_I] + [_P] * 11 + [_I, _I, _I, _P]
+_BS_BLOCKS_SIG = [_I] + [_P] * 8 + [_I, _I, _P]
+
+
+def _schur_pcg_plan(ia, ib, Na, Nb):
+    """sort orders, CSR pointers, cross positions and work items of csrc/ba_schur.hip for one index structure (int32)"""
+    dev, E = ia.device, ia.numel()
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    ar = lambda n: torch.arange(n, device=dev)
+
+    def csr(idx, n):
+        cnt = torch.bincount(idx, minlength=n)
+        ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        ptr[1:] = torch.cumsum(cnt, 0)
+        return cnt, ptr
+    permP = torch.argsort(ia, stable=True)
+    permC = torch.argsort(ib * Na + ia, stable=True)                 # by kept row, then eliminated row: a pair's observations adjacent
+    cntP, ptrP = csr(ia, Na)
+    cntC, ptrC = csr(ib, Nb)
+    posP, posC = torch.empty_like(permP), torch.empty_like(permC)
+    posP[permP], posC[permC] = ar(E), ar(E)
+    # eliminated rows: lane groups of G = 2^lg lanes, 64 / G rows per wavefront; more than 64 observations: a workgroup
+    lg = sum((cntP > (1 << b)).long() for b in range(6))
+    short = cntP <= 64
+    witems, plist, off = [], [], 0
+    for g in range(7):
+        pts = ((lg == g) & short).nonzero().reshape(-1)
+        n, per = pts.numel(), 64 >> g
+        if n:
+            first = ar((n + per - 1) // per) * per
+            witems.append(torch.stack([torch.full_like(first, g), off + first, (n - first).clamp(max=per)], 1))
+            plist.append(pts)
+            off += n
+    some = lambda ts, w: torch.cat(ts) if ts else torch.zeros((1,) + w, dtype=torch.int64, device=dev)
+    long_ = (~short).nonzero().reshape(-1)
+    # kept rows: ranges of at most SCHUR_CCHUNK camera-major observations, at least one (possibly empty) item per row
+    per = ((cntC + SCHUR_CCHUNK - 1) // SCHUR_CCHUNK).clamp(min=1)
+    cfirst = torch.cumsum(per, 0) - per
+    row = torch.repeat_interleave(ar(Nb), per)
+    beg = ptrC[row] + (ar(row.numel()) - cfirst[row]) * SCHUR_CCHUNK
+    citems = torch.stack([row, beg, torch.minimum(beg + SCHUR_CCHUNK, ptrC[row + 1])], 1)
+    return dict(ia=ia.clone(), ib=ib.clone(), permP=i32(permP), permC=i32(permC), ptrP=i32(ptrP), ptrC=i32(ptrC), camP=i32(ib[permP]),
+                posPC=i32(posC[permP]), posCP=i32(posP[permC]), ptC=i32(ia[permC]), plist=i32(some(plist, ())),
+                witems=i32(some(witems, (3,))), nW=sum(w.shape[0] for w in witems), litems=i32(long_ if long_.numel() else some([], ())),
+                nL=long_.numel(), citems=i32(citems), nI=citems.shape[0], cfirst=i32(cfirst), cnitems=i32(per))
+
+
+class _SchurWorkspace:
+    """device buffers of one problem shape (cached in ``opt._pcg_workspaces``); the library never allocates"""
+
+    def __init__(self, E, Na, Nb, mb, nI, check_every, dt, dev):
+        z = lambda *s: torch.zeros(s, dtype=dt, device=dev)
+        zi = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)
+        self.JP, self.rP, self.JC, self.u = z(E, 2 * (mb + 3)), z(E, 2), z(E, 2 * mb), z(E, 2)
+        self.Vinv, self.sa, self.xa = z(Na, 6), z(Na, 3), z(Na, 3)
+        self.Scc, self.Minv, self.sb = z(Nb, mb, mb), z(Nb, mb, mb), z(Nb, mb)
+        self.x, self.r, self.p, self.q, self.z, self.b, self.zero, self.xin = (z(Nb, mb) for _ in range(8))
+        self.part, self.dots, self.wpart = z(nI, mb), z(Nb), z(2 * ((Nb + 15) // 16))
+        self.scal, self.hist = z(8), z(check_every + 1)
+        self.ccnt, self.gcnt = zi(Nb), zi(2)
+        self.packed = None
+
+
+class _SchurHip:
+    """the same operators through csrc/ba_schur.hip (dr = 2, eliminated width 3, kept width 6 | 9)"""
+
+    def __init__(self, lin, G, shift, precond, every=8):
+        self.lin, self.precond, self.G = lin, precond, G
+        self.Na, self.Nb, self.mb = G["Na"], G["Nb"], G["mb"]
+        dt, dev = lin.R.dtype, lin.R.device
+        self.sfx = "_f32" if dt == torch.float32 else "_f64"
+        opt = lin.opt.__dict__ if hasattr(lin.opt, '__dict__') else {}
+        plans = opt.setdefault('_schur_pcg_plans', {})
+        pl = plans.get((lin.E, self.Na, self.Nb))
+        if pl is None or not (torch.equal(pl["ia"], G["ia"]) and torch.equal(pl["ib"], G["ib"])):
+            pl = plans[(lin.E, self.Na, self.Nb)] = _schur_pcg_plan(G["ia"], G["ib"], self.Na, self.Nb)
+        self.pl = pl
+        key = ("schur-pcg", lin.E, self.Na, self.Nb, self.mb, pl["nI"], every, dt, dev)
+        cache = opt.setdefault('_pcg_workspaces', {})
+        w = cache.get(key)
+        if w is None:
+            w = cache[key] = _SchurWorkspace(lin.E, self.Na, self.Nb, self.mb, pl["nI"], every, dt, dev)
+        self.w, self.every = w, every
+        cat_p = lambda ks: torch.cat([shift[lin.slots[k][0]] for k in ks], dim=-1)
+        if w.packed is None or w.packed() is not lin:          # once per linearisation (the trial loop re-damps the same one)
+            self._call("pack", _BS_PACK_SIG, *self._pack_args())
+            w.packed = weakref.ref(lin)
+        w.sa.copy_(cat_p(G["a"]))
+        w.sb.copy_(cat_p(G["b"]))
+        self._point(3)
+        pl_ = self.pl
+        self._call("blocks", _BS_BLOCKS_SIG, self.mb, w.JP.data_ptr(), pl_["posCP"].data_ptr(), pl_["ptC"].data_ptr(), pl_["ptrC"].data_ptr(),
+                   w.Vinv.data_ptr(), w.sb.data_ptr(), w.Scc.data_ptr(), w.Minv.data_ptr(), self.Nb, 1 if precond == "schur" else 0)
+
+    def _call(self, name, sig, *args):
+        dev = self.lin.R.device
+        with _C._on_device(dev):
+            _C.check(_C.library().symbol("pplie_ba_schur_" + name + self.sfx, sig)(*args, _C.stream_ptr(dev)), "pplie_ba_schur_" + name)
+
+    def _pack_args(self):
+        lin, G, w, pl = self.lin, self.G, self.w, self.pl
+        self._Jk = [lin.slots[k][2].contiguous() for k in G["b"]]                 # (kept alive until the launch is enqueued)
+        self._Ja = lin.slots[G["a"][0]][2].contiguous()
+        n = len(self._Jk)
+        return (n, (ctypes.c_void_p * n)(*[J.data_ptr() for J in self._Jk]), (ctypes.c_int * n)(*[J.shape[-1] for J in self._Jk]),
+                self._Ja.data_ptr(), lin.R.data_ptr(), pl["permP"].data_ptr(), pl["permC"].data_ptr(), w.JP.data_ptr(), w.rP.data_ptr(),
+                w.JC.data_ptr(), lin.E, lin.dr, self._Ja.shape[-1])
+
+    def _point(self, mode, A=None, B=None):
+        w, pl = self.w, self.pl
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self._call("point", _BS_POINT_SIG, mode, self.mb, w.JP.data_ptr(), w.rP.data_ptr(), pl["camP"].data_ptr(), pl["posPC"].data_ptr(),
+                   pl["ptrP"].data_ptr(), pl["plist"].data_ptr(), pl["witems"].data_ptr(), pl["nW"], pl["litems"].data_ptr(), pl["nL"],
+                   ptr(A), ptr(B), w.scal.data_ptr(), w.Vinv.data_ptr(), w.sa.data_ptr(), w.u.data_ptr(), w.xa.data_ptr(), self.Nb)
+
+    def _cam(self, A, B, q, neg=0):
+        w, pl = self.w, self.pl
+        self._call("cam", _BS_CAM_SIG, self.mb, w.JC.data_ptr(), w.u.data_ptr(), pl["citems"].data_ptr(), pl["nI"], pl["cfirst"].data_ptr(),
+                   pl["cnitems"].data_ptr(), w.part.data_ptr(), w.ccnt.data_ptr(), w.gcnt.data_ptr(), A.data_ptr(),
+                   None if B is None else B.data_ptr(), w.sb.data_ptr(), q.data_ptr(), w.dots.data_ptr(), w.scal.data_ptr(), self.Nb, neg)
+
+    def _step(self, k, init=0):
+        w = self.w
+        self._call("step", _BS_STEP_SIG, self.mb, w.x.data_ptr(), w.r.data_ptr(), w.p.data_ptr(), w.q.data_ptr(), w.z.data_ptr(),
+                   w.Minv.data_ptr(), w.b.data_ptr(), w.scal.data_ptr(), w.wpart.data_ptr(), w.gcnt[1:].data_ptr(), w.hist.data_ptr(), k, self.Nb,
+                   init)
+
+    def S(self, x):
+        self.w.xin.copy_(x)
+        self._point(0, self.w.xin)
+        out = torch.empty_like(self.w.xin)
+        self._cam(self.w.xin, None, out)
+        return out
+
+    def b_S(self):
+        self._point(1)
+        self._cam(self.w.zero, None, self.w.b, neg=1)
+        return self.w.b.clone()
+
+    def blocks(self):
+        return self.w.Scc.clone(), self.w.Minv.clone()
+
+    def back(self, x):
+        self.w.xin.copy_(x)
+        self._point(2, self.w.xin)
+        return self.w.xa.clone()
+
+    def solve(self, solver):
+        """three launches per iteration, alpha / beta / |r|^2 on the device; the host reads |r|^2 once per ``check_every``"""
+        w, every = self.w, self.every
+        self.b_S()
+        self._step(0, init=1)
+        bn2 = float(w.hist[0])
+        maxiter = self.Nb * self.mb * 10 if solver.maxiter is None else solver.maxiter
+        done = 0
+        while bn2 > 0.0 and done < maxiter:
+            for k in range(every):
+                self._point(0, w.z, w.p)                   # u = Pi Jc (z + beta p)
+                self._cam(w.z, w.p, w.q)                   # p = z + beta p, q = S p, alpha
+                self._step(1 + k)                          # x, r, z, rho, beta, |r|^2
+            done += every
+            rr = float(w.hist[every])
+            if rr <= solver.tol * solver.tol * bn2 or rr != rr:
+                break
+        solver.iterations = done
+        xb = w.x.clone()
+        return self.lin._schur_split(self.back(xb), xb)

@@ -263,6 +263,19 @@ class PCG(nn.Module):
         return self.solve(lambda v: A @ v, b, lambda v: v / d)
 
 
+class SchurPCG(PCG):
+    """PCG on the reduced system of a bipartite problem (bundle adjustment: the points eliminated, S = U - W V^-1 W^T applied
+    implicitly; optim/multigraph.py, csrc/ba_schur.hip).  Stops when ||r_S|| <= tol * ||b_S|| on the REDUCED system.
+    ``precond``: "schur" = the block diagonal of S, "jacobi" = the block diagonal of U + shift.  On any other problem (not
+    bipartite, weighted, sharded) it is the full-system ``PCG`` it derives from."""
+
+    def __init__(self, maxiter=None, tol=1e-5, check_every=8, precond="schur"):
+        super().__init__(maxiter=maxiter, tol=tol, check_every=check_every)
+        if precond not in ("schur", "jacobi"):
+            raise ValueError(f"SchurPCG: precond must be 'schur' or 'jacobi', got {precond!r}")
+        self.precond = precond
+
+
 def _all_reduce(t, group):
     if group is not None:
         import torch.distributed as dist
