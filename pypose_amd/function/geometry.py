@@ -11,6 +11,10 @@ algebra is plain tensor arithmetic on whatever device the inputs live on.
 ``bal_point2pixel`` / ``bal_reprojerr`` are the Snavely / BAL model of the reference's bundle-adjustment example (focal length
 and two radial distortion coefficients per camera) the same way (csrc/bal.hip): ``pplie_se3_bal_lin`` returns the residual and
 the blocks for intrinsics, pose and point, ``pplie_bal_vjp`` contracts all three.
+
+``knn`` (reference geometry.py:228-313) streams the neighbour cloud through LDS and keeps every reference point's best k in
+registers (csrc/knn.hip): the ``[N1, N2]`` distance matrix of the reference formulation is never formed.  ``_icp_stats`` is the
+same pass with the sums one ICP iteration needs (module/icp.py).
 """
 import ctypes
 
@@ -334,6 +338,120 @@ def bal_reprojerr(points, pixels, intrinsics, extrinsics, reduction='none'):
     _need(reduction in {'norm', 'sum', 'none'}, "Reduction method can only be 'norm'|'sum'|'none'.")
     err = _bal_project(points, intrinsics, extrinsics, pixels)
     return {'none': lambda e: e, 'norm': lambda e: e.norm(dim=-1), 'sum': lambda e: e.sum(dim=-1)}[reduction](err)
+
+
+# ---- nearest neighbours and ICP correspondences (csrc/knn.hip)
+_KNN_BLOCK, _KNN_TILE, _KNN_MAXK = 256, 1024, 16
+_KNN_PARTIAL_SIG = [ctypes.c_void_p] * 7 + [ctypes.c_int64] * 3 + [ctypes.c_int] * 2 + [ctypes.c_int64] * 2 + [ctypes.c_void_p]
+_KNN_MERGE_SIG = [ctypes.c_void_p] * 10 + [ctypes.c_int64] * 3 + [ctypes.c_int] * 2 + [ctypes.c_int64] * 2 + [ctypes.c_void_p]
+_KNN_CHUNK = 1 << 24          # elements of the tensor formulation's [chunk, N2, D] temporary
+
+
+def _knn_on_kernels(ref, nbr, k, ord, dim, largest):
+    """the kernels take 3-D HIP clouds of one dtype (fp32 / fp64), the Euclidean norm over the last dimension and the
+    k <= 16 smallest; everything else is the tensor formulation's"""
+    return (_C._test_backend is None and ref.is_cuda and nbr.is_cuda and ref.device == nbr.device and ref.dtype == nbr.dtype
+            and ref.dtype in _C._SUFFIX and ref.dim() >= 2 and nbr.dim() >= 2 and ref.shape[-1] == 3 and nbr.shape[-1] == 3
+            and ord == 2 and dim == -1 and not largest and 1 <= k <= _KNN_MAXK and ref.shape[-2] > 0
+            and 0 < nbr.shape[-2] < 2 ** 31 and ref.shape[-2] < 2 ** 31
+            and 0 < torch.broadcast_shapes(ref.shape[:-2], nbr.shape[:-2]).numel() <= 65535)
+
+
+def _knn_flat(t, batch):
+    """``t [..., N, 3]`` as contiguous rows and its batch stride in points: a cloud shared by the whole batch is not copied
+    (stride 0)"""
+    n = t.shape[-2]
+    if t.shape[:-2].numel() == 1:
+        return t.reshape(n, 3).contiguous(), 0
+    return t.expand(batch + (n, 3)).reshape(-1, n, 3).contiguous(), n
+
+
+def _knn_launch(ref, rs, nbr, ns, B, k, T=None, splits=None, stats=None):
+    """partial pass (+ merge pass) on flattened clouds.  Returns (values, indices) ``[B, N1, k]``, or with ``stats`` (a dict
+    that keeps the scratch of an ICP loop between iterations) the 16 fp64 sums ``[B, 16]`` of the k = 1 correspondences."""
+    N1, N2, dev, dt = ref.shape[-2], nbr.shape[-2], ref.device, ref.dtype
+    nt = -(-N2 // _KNN_TILE)
+    S = splits if splits is not None else -(-512 // (B * -(-N1 // _KNN_BLOCK)))       # about two workgroups per CU
+    S = max(1, min(S, nt))
+    lib, sfx = _C.library(), _C._SUFFIX[dt]
+    partial = lib.symbol("pplie_knn_partial" + sfx, _KNN_PARTIAL_SIG)
+    merge = lib.symbol("pplie_knn_merge" + sfx, _KNN_MERGE_SIG)
+    tp = None if T is None else T.data_ptr()
+    with _C._on_device(dev):
+        st = _C.stream_ptr(dev)
+        if stats is None:
+            values = torch.empty((B, N1, k), dtype=dt, device=dev)
+            indices = torch.empty((B, N1, k), dtype=torch.int64, device=dev)
+            if S == 1:
+                _C.check(partial(ref.data_ptr(), nbr.data_ptr(), tp, None, None, values.data_ptr(), indices.data_ptr(), B, N1, N2, k, 1,
+                                 rs, ns, st), "pplie_knn_partial" + sfx)
+                return values, indices
+        key = (B, S, N1, k, dt, dev)
+        if stats is None or stats.get("key") != key:
+            ws = {"key": key, "pd2": torch.empty((B, S, N1, k), dtype=dt, device=dev),
+                  "pidx": torch.empty((B, S, N1, k), dtype=torch.int32, device=dev)}
+            if stats is not None:
+                ws.update(wg=torch.empty((B, -(-N1 // _KNN_BLOCK), 16), dtype=torch.float64, device=dev),
+                          cnt=torch.zeros(B, dtype=torch.int32, device=dev))        # the kernel leaves the counters zero
+                stats.clear()
+                stats.update(ws)
+        else:
+            ws = stats
+        _C.check(partial(ref.data_ptr(), nbr.data_ptr(), tp, ws["pd2"].data_ptr(), ws["pidx"].data_ptr(), None, None, B, N1, N2, k, S,
+                         rs, ns, st), "pplie_knn_partial" + sfx)
+        if stats is None:
+            _C.check(merge(ws["pd2"].data_ptr(), ws["pidx"].data_ptr(), values.data_ptr(), indices.data_ptr(), None, None, None, None,
+                           None, None, B, N1, N2, k, S, rs, ns, st), "pplie_knn_merge" + sfx)
+            return values, indices
+        sums = torch.empty((B, 16), dtype=torch.float64, device=dev)
+        _C.check(merge(ws["pd2"].data_ptr(), ws["pidx"].data_ptr(), None, None, ref.data_ptr(), nbr.data_ptr(), tp, ws["wg"].data_ptr(),
+                       ws["cnt"].data_ptr(), sums.data_ptr(), B, N1, N2, 1, S, rs, ns, st), "pplie_knn_merge" + sfx)
+        return sums
+
+
+def _icp_stats(source, ss, target, ts, T, B, ws, splits=None):
+    """per batch element, over the nearest target point q of every p = T . source: ``[sum d, sum p (3), sum q (3),
+    sum q p^T (9)]`` in fp64 ``[B, 16]`` -- two launches, the moved cloud is never written"""
+    return _knn_launch(source, ss, target, ts, B, 1, T=T, splits=splits, stats=ws)
+
+
+def _knn_tensor(ref, nbr, k, ord, dim, largest, sorted):
+    """the reference's formulation, norm(ref[..., :, None, :] - nbr[..., None, :, :]).topk, in chunks of reference points so
+    that the temporary stays bounded (any device, width, norm and dtype; ``largest``; k > 16)"""
+    def one(r):
+        return torch.linalg.norm(r.unsqueeze(-2) - nbr.unsqueeze(-3), dim=dim, ord=ord).topk(k, dim=dim, largest=largest, sorted=sorted)
+    n1 = ref.shape[-2]
+    lead = torch.broadcast_shapes(ref.shape[:-2], nbr.shape[:-2]).numel()
+    chunk = max(1, _KNN_CHUNK // max(1, lead * nbr.shape[-2] * max(ref.shape[-1], nbr.shape[-1])))
+    if dim != -1 or n1 <= chunk:
+        return one(ref)
+    parts = [one(ref[..., i:i + chunk, :]) for i in range(0, n1, chunk)]
+    return torch.return_types.topk((torch.cat([p.values for p in parts], -2), torch.cat([p.indices for p in parts], -2)))
+
+
+def knn(ref, nbr, k=1, ord=2, dim=-1, largest=False, sorted=True, _splits=None):
+    """The ``k`` nearest (``largest``: furthest) points of ``nbr (..., N2, D)`` for every point of ``ref (..., N1, D)`` in the
+    ``ord``-norm: ``torch.return_types.topk(values, indices)``, both ``(..., N1, k)`` (reference geometry.py:228-313).
+
+    3-D clouds of one dtype (fp32 / fp64) on the device with ``ord=2, dim=-1, largest=False, k <= 16`` run in csrc/knn.hip: the
+    neighbour cloud is streamed through LDS, every reference point keeps its best k in registers, and the ``[N1, N2]``
+    distance matrix is never formed; equal distances go to the smaller index.  Everything else takes the tensor formulation.
+    When a gradient is recorded the indices come from the kernels and the values are recomputed from the gathered
+    neighbours, which gives the reference's gradients in O(N1 k) work."""
+    if not _knn_on_kernels(ref, nbr, k, ord, dim, largest):
+        return _knn_tensor(ref, nbr, k, ord, dim, largest, sorted)
+    n1, n2 = ref.shape[-2], nbr.shape[-2]
+    if k > n2:
+        raise RuntimeError("selected index k out of range")
+    batch = torch.broadcast_shapes(ref.shape[:-2], nbr.shape[:-2])
+    r, rs = _knn_flat(ref.detach(), batch)
+    n, ns = _knn_flat(nbr.detach(), batch)
+    values, indices = _knn_launch(r, rs, n, ns, batch.numel(), k, splits=_splits)
+    values, indices = values.view(batch + (n1, k)), indices.view(batch + (n1, k))
+    if torch.is_grad_enabled() and (ref.requires_grad or nbr.requires_grad):
+        picked = torch.gather(nbr.expand(batch + (n2, 3)), -2, indices.reshape(batch + (n1 * k, 1)).expand(batch + (n1 * k, 3)))
+        values = torch.linalg.norm(ref.unsqueeze(-2) - picked.view(batch + (n1, k, 3)), dim=-1)
+    return torch.return_types.topk((values, indices))
 
 
 def _centred(points):

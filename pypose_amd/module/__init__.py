@@ -1,2 +1,3 @@
 from .imu_preintegrator import IMUPreintegrator
 from .loss import GeodesicLoss, geodesic_loss
+from .icp import ICP
