@@ -15,8 +15,13 @@ the blocks for intrinsics, pose and point, ``pplie_bal_vjp`` contracts all three
 ``knn`` (reference geometry.py:228-313) streams the neighbour cloud through LDS and keeps every reference point's best k in
 registers (csrc/knn.hip): the ``[N1, N2]`` distance matrix of the reference formulation is never formed.  ``_icp_stats`` is the
 same pass with the sums one ICP iteration needs (module/icp.py).
+
+``nbr_filter`` / ``knn_filter`` / ``voxel_filter`` (reference geometry.py:436-664) are the steps before registration
+(csrc/cloud_filter.hip): the cloud streamed against itself with a count under the radius kept next to the best-k list, and voxel
+keys plus a segmented mean over the sorted keys.  ``random_filter`` is an index.
 """
 import ctypes
+import math
 
 import torch
 
@@ -452,6 +457,216 @@ def knn(ref, nbr, k=1, ord=2, dim=-1, largest=False, sorted=True, _splits=None):
         picked = torch.gather(nbr.expand(batch + (n2, 3)), -2, indices.reshape(batch + (n1 * k, 1)).expand(batch + (n1 * k, 3)))
         values = torch.linalg.norm(ref.unsqueeze(-2) - picked.view(batch + (n1, k, 3)), dim=-1)
     return torch.return_types.topk((values, indices))
+
+
+# ---- point-cloud filters (csrc/cloud_filter.hip)
+_CF_MAXD = 8
+_CF_PARTIAL_SIG = [ctypes.c_void_p] * 4 + [ctypes.c_int64] * 2 + [ctypes.c_double] + [ctypes.c_int] * 2 + [ctypes.c_void_p]
+_CF_FINISH_SIG = [ctypes.c_void_p] * 6 + [ctypes.c_int64] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
+_CF_KEYS_SIG = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int] + [ctypes.c_double] * 3 + [ctypes.c_void_p] * 4
+_CF_HEADS_SIG = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+_CF_REDUCE_SIG = [ctypes.c_void_p] * 10 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
+
+
+def _filter_on_kernels(points, width, ord=2, kk=0):
+    """the kernels take HIP clouds (fp32 / fp64) of row width 3..8 whose first three columns are the coordinates, the Euclidean
+    norm and lists of at most 16; everything else is the tensor formulation's"""
+    return (_C._test_backend is None and points.is_cuda and points.dtype in _C._SUFFIX and ord == 2 and width == 3
+            and 3 <= points.shape[-1] <= _CF_MAXD and 0 < points.shape[-2] < 2 ** 31 and kk <= _KNN_MAXK
+            and 0 < points.shape[:-2].numel() <= 65535)
+
+
+def _radius2(radius, dtype):
+    """r^2 = radius * radius rounded once in the cloud's dtype, or None where the kernels' d^2 <= r^2 would not be the
+    reference's d <= radius (a negative, infinite or NaN radius, an r^2 that overflows)"""
+    r = torch.tensor(float(radius), dtype=dtype)
+    r2 = (r * r).item()
+    return r2 if radius >= 0 and r2 != float("inf") and r2 == r2 else None
+
+
+def _nbr_launch(points, r2, kk, nbr, splits=None):
+    """self-neighbourhood pass and finish on ``points [B, N, D]``: the keep mask ``[B, N]`` (count - 1 >= nbr) and, for
+    ``kk > 0``, the mean ``[B, N, D]`` over every point's kk nearest (itself among them)"""
+    B, N, D = points.shape
+    dev, dt = points.device, points.dtype
+    cloud = points.contiguous()
+    xyz = cloud if D == 3 else points[..., :3].contiguous()
+    S = splits if splits is not None else -(-512 // (B * -(-N // _KNN_BLOCK)))        # about two workgroups per CU
+    S = max(1, min(S, -(-N // _KNN_TILE)))
+    lib, sfx = _C.library(), _C._SUFFIX[dt]
+    pcount = torch.empty((B, S, N), dtype=torch.int32, device=dev)
+    pd2 = torch.empty((B, S, N, kk), dtype=dt, device=dev) if kk else None
+    pidx = torch.empty((B, S, N, kk), dtype=torch.int32, device=dev) if kk else None
+    mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    mean = torch.empty((B, N, D), dtype=dt, device=dev) if kk else None
+    ptr = lambda t: None if t is None else t.data_ptr()                               # noqa: E731
+    nbr = max(-2 ** 31, min(math.ceil(nbr), 2 ** 31 - 1))                             # (counts are integers below 2^31)
+    with _C._on_device(dev):
+        st = _C.stream_ptr(dev)
+        _C.check(lib.symbol("pplie_nbr_partial" + sfx, _CF_PARTIAL_SIG)(xyz.data_ptr(), pcount.data_ptr(), ptr(pd2), ptr(pidx), B, N,
+                                                                        r2, kk, S, st), "pplie_nbr_partial" + sfx)
+        _C.check(lib.symbol("pplie_nbr_finish" + sfx, _CF_FINISH_SIG)(pcount.data_ptr(), ptr(pd2), ptr(pidx), ptr(cloud if kk else None),
+                                                                      mask.data_ptr(), ptr(mean), B, N, D, kk, S, nbr, st),
+                 "pplie_nbr_finish" + sfx)
+    return mask.bool(), mean
+
+
+def _nbr_count_tensor(xyz, radius, ord):
+    """``#{j : |x_i - x_j| <= radius}`` (the point itself included) the reference's way, in chunks of rows"""
+    n = xyz.shape[-2]
+    chunk = max(1, _KNN_CHUNK // max(1, n * xyz.shape[-1]))
+    return torch.cat([(torch.linalg.norm(xyz[i:i + chunk].unsqueeze(-2) - xyz.unsqueeze(-3), dim=-1, ord=ord) <= radius).sum(-1)
+                      for i in range(0, n, chunk)]) if n else xyz.new_zeros((0,), dtype=torch.int64)
+
+
+def nbr_filter(points, nbr, radius, pdim=None, ord=2, return_mask=False, _splits=None):
+    """Drop the points of ``points (N, D)`` that have fewer than ``nbr`` neighbours within ``radius`` (``ord``-norm over the first
+    ``pdim`` columns, default all of them): the kept rows in input order and, with ``return_mask``, the mask ``(N,)`` (reference
+    geometry.py:436-493).  Point i is kept when ``#{j : d(i, j) <= radius} - 1 >= nbr``, the count including i itself.
+
+    HIP clouds (fp32 / fp64) with ``pdim == 3``, ``ord == 2`` and ``3 <= D <= 8`` run in csrc/cloud_filter.hip: the cloud is
+    streamed against itself through LDS and the ``[N, N]`` distance matrix is never formed.  The kernel compares
+    ``d^2 <= r^2`` with ``r^2 = radius * radius`` rounded once in the cloud's dtype, which can differ from the reference's
+    ``sqrt(...) <= radius`` only for pairs within a few ulp of the radius.  Everything else takes the tensor formulation."""
+    assert len(points.shape) == 2, "The point cloud dimension has to be 2."
+    pdim = points.size(-1) if pdim is None else pdim
+    assert points.size(-1) >= pdim, "The last dim of points should not less than pdim."
+    r2 = _radius2(radius, points.dtype) if _filter_on_kernels(points, pdim, ord) else None
+    if r2 is not None:
+        mask = _nbr_launch(points.detach().unsqueeze(0), r2, 0, nbr, _splits)[0][0]
+    else:
+        mask = _nbr_count_tensor(points[..., :pdim].detach(), radius, ord) - 1 >= nbr
+    return (points[mask], mask) if return_mask else points[mask]
+
+
+def random_filter(points, num):
+    """``num`` points of ``points (..., N, D)`` drawn without replacement, the same draw for every batch element:
+    ``(..., num, D)`` (reference geometry.py:496-527)."""
+    assert points.size(-1) >= 1, "The last dim of the points should not less than 1."
+    assert num <= points.size(-2), "Number of points to sample must not larger than the number of input points."
+    indices = torch.randperm(points.size(-2))[:num]
+    return points[..., indices, :]
+
+
+def _voxel_tensor(points, voxel, random):
+    """the reference's result from torch.unique over the int64 cell triples (any device, width and dtype)"""
+    vdim = len(voxel)
+    xyz = points[..., :vdim]
+    cells = ((xyz - xyz.min(dim=-2).values) / torch.tensor(voxel, dtype=torch.float32, device=points.device)).to(torch.int64)
+    uniq, inverse, counts = torch.unique(cells, dim=-2, return_inverse=True, return_counts=True)
+    if random:
+        order = torch.argsort(inverse, stable=True)
+        pick = (torch.rand(counts.shape[0], device=points.device) * counts).long().clamp(max=counts - 1)
+        return points[order[pick + torch.cumsum(counts, dim=0) - counts]]
+    sums = points.new_zeros((uniq.shape[0], points.shape[-1])).index_add_(0, inverse, points)
+    return sums / counts.to(points.dtype).view(-1, 1)
+
+
+def _voxel_launch(cloud, voxel):
+    """keys, sort and segmented mean on ``cloud [N, D]``: (means ``[M, D]``, the sort's permutation ``[N]``, start ``[M]``,
+    count ``[M]`` of every cell's run in the sorted order), cells in ascending (i0, i1, i2); None when a cell index does not
+    fit 21 bits.  One host read: M together with the overflow flag."""
+    N, D = cloud.shape
+    dev, dt = cloud.device, cloud.dtype
+    lib, sfx = _C.library(), _C._SUFFIX[dt]
+    nwg = -(-N // 256)
+    keys = torch.empty(N, dtype=torch.int64, device=dev)
+    part = torch.empty((256, 3), dtype=dt, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    heads = torch.empty(nwg, dtype=torch.int32, device=dev)
+    v = [float(torch.tensor(s, dtype=torch.float32)) for s in voxel]                  # rounded to float32, as the reference's
+    if not all(0 < s < float("inf") for s in v):
+        return None
+    with _C._on_device(dev):
+        st = _C.stream_ptr(dev)
+        _C.check(lib.symbol("pplie_voxel_keys" + sfx, _CF_KEYS_SIG)(cloud.data_ptr(), N, D, v[0], v[1], v[2], part.data_ptr(),
+                                                                    keys.data_ptr(), flag.data_ptr(), st), "pplie_voxel_keys" + sfx)
+        keys, perm = torch.sort(keys, stable=True)
+        _C.check(lib.symbol("pplie_voxel_heads", _CF_HEADS_SIG)(keys.data_ptr(), N, heads.data_ptr(), st), "pplie_voxel_heads")
+        total = torch.cumsum(heads, dim=0)
+        base = total - heads
+        M, bad = torch.stack([total[-1], flag[0].to(torch.int64)]).tolist()
+        if bad:
+            return None
+        out = torch.empty((M, D), dtype=dt, device=dev)
+        start = torch.empty(M, dtype=torch.int32, device=dev)
+        count = torch.empty(M, dtype=torch.int32, device=dev)
+        lead = torch.empty((nwg, 16), dtype=torch.float64, device=dev)
+        tail = torch.empty((nwg, 16), dtype=torch.float64, device=dev)
+        info = torch.empty((nwg, 4), dtype=torch.int32, device=dev)
+        _C.check(lib.symbol("pplie_voxel_reduce" + sfx, _CF_REDUCE_SIG)(keys.data_ptr(), perm.data_ptr(), cloud.data_ptr(), base.data_ptr(),
+                                                                        lead.data_ptr(), tail.data_ptr(), info.data_ptr(), out.data_ptr(),
+                                                                        start.data_ptr(), count.data_ptr(), N, D, st),
+                 "pplie_voxel_reduce" + sfx)
+    return out, perm, start, count
+
+
+def voxel_filter(points, voxel, random=False):
+    """One point per occupied voxel of ``points (N, D)``: the mean of all D columns of the voxel's points, or with ``random`` one
+    of them; ``(M, D)`` (reference geometry.py:530-602).  ``voxel`` lists the cell sizes of the first ``len(voxel)`` columns.  The
+    cell of a point is ``trunc((p - min) / v)`` with ``min`` the column minima of the cloud and ``v`` the sizes rounded to float32
+    (the reference builds ``torch.tensor(voxel)``); rows come in ascending lexicographic order of the cell indices, the order of
+    ``torch.unique(dim=-2)``.
+
+    HIP clouds (fp32 / fp64) with three positive voxel sizes and ``3 <= D <= 8`` run in csrc/cloud_filter.hip: the cell indices
+    (bit-identical to the tensor formulation's) are packed into one int64 key of 3 x 21 bits, sorted, and the means come from a
+    segmented scan in fp64 with a fixed order -- no floating-point atomics, two calls give the same bits.  With ``random`` the
+    member is drawn with ``torch.rand`` over the run lengths; it is not the reference's draw.  A cloud with more than 2^21
+    cells along a column, and everything else, takes the tensor formulation; so does a cloud that records a gradient."""
+    assert len(points.shape) == 2, "The point cloud dimension has to be 2."
+    D, vdim = points.size(-1), len(voxel)
+    assert D >= vdim, "The last dimension of the pointcloud should exceed the dimenson of the voxel space."
+    assert all(item != 0 for item in voxel), "Voxel size should be nonzero."
+    if _filter_on_kernels(points, vdim) and all(item > 0 for item in voxel) and not (torch.is_grad_enabled() and points.requires_grad):
+        res = _voxel_launch(points.detach().contiguous(), voxel)
+        if res is not None:
+            out, perm, start, count = res
+            if not random:
+                return out
+            pick = (torch.rand(count.shape[0], device=points.device) * count).long().clamp(max=count - 1)
+            return points[perm[start + pick]]
+    return _voxel_tensor(points, voxel, random)
+
+
+def _knn_mean_tensor(points, xyz, kk, ord):
+    """mean over every point's kk nearest (itself among them), searched in and gathered from the whole cloud"""
+    idx = _knn_tensor(xyz, xyz, kk, ord, -1, False, True).indices
+    n, D = points.shape[-2:]
+    picked = torch.gather(points, -2, idx.reshape(idx.shape[:-2] + (n * kk, 1)).expand(idx.shape[:-2] + (n * kk, D)))
+    return picked.view(points.shape[:-1] + (kk, D)).mean(dim=-2)
+
+
+def knn_filter(points, k, pdim=None, radius=None, ord=2, _splits=None):
+    """Smooth ``points (..., N, D)``: every point becomes the mean, over all D columns, of itself and its ``k`` nearest
+    neighbours (``ord``-norm over the first ``pdim`` columns); with ``radius`` (then ``points`` is ``(N, D)``) only the points
+    with at least ``k`` neighbours within ``radius`` are kept, in input order (reference geometry.py:605-664).
+
+    The k + 1 nearest are searched in the whole input cloud, the point itself among them, and are gathered from it by original
+    index; the mean is written for the survivors only.  (The reference gathers from the already compacted cloud with indices of
+    the uncompacted one, which agrees with this where the survivors form a prefix of the cloud, as in its example.)  Equal
+    distances go to the smaller index.
+
+    HIP clouds (fp32 / fp64) with ``pdim == 3``, ``ord == 2``, ``3 <= D <= 8`` and ``k + 1 <= 16`` run in csrc/cloud_filter.hip:
+    one streaming pass over the pairs keeps the count under the radius (``d^2 <= r^2``, ``r^2 = radius * radius`` rounded once in
+    the cloud's dtype) next to the best k + 1, and the means are accumulated in fp64.  Everything else, and a cloud that records
+    a gradient, takes the tensor formulation."""
+    if radius is not None:
+        assert len(points.shape) == 2, "The points dimension has to be 2 given radius."
+    else:
+        assert len(points.shape) >= 2, "The points dimension cannot be less than 2."
+    pdim = points.size(-1) if pdim is None else pdim
+    assert points.size(-1) >= pdim, "The last dim of points should not less than pdim."
+    n, D = points.shape[-2:]
+    on_kernels = _filter_on_kernels(points, pdim, ord, k + 1) and k >= 0 and not (torch.is_grad_enabled() and points.requires_grad)
+    r2 = -1.0 if radius is None else _radius2(radius, points.dtype) if on_kernels else None
+    if k + 1 > n and n > 0:
+        raise RuntimeError("selected index k out of range")
+    if on_kernels and r2 is not None:
+        mask, mean = _nbr_launch(points.detach().reshape(-1, n, D), r2, k + 1, k, _splits)
+        return mean.view(points.shape) if radius is None else mean[0][mask[0]]
+    xyz = points[..., :pdim]
+    mean = _knn_mean_tensor(points, xyz, k + 1, ord)
+    return mean if radius is None else mean[_nbr_count_tensor(xyz.detach(), radius, ord) - 1 >= k]
 
 
 def _centred(points):
