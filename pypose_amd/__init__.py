@@ -26,7 +26,7 @@ from . import function
 from . import testing
 from . import func
 from .function import cart2homo, homo2cart, point2pixel, pixel2point, reprojerr, is_lietensor, is_SE3, hasnan, chspline, bspline, svdtf, svdstf, \
-    bvv, bmv, bvmv, bal_point2pixel, bal_reprojerr, knn, nbr_filter, random_filter, voxel_filter, knn_filter
+    bvv, bmv, bvmv, bal_point2pixel, bal_reprojerr, knn, nbr_filter, random_filter, voxel_filter, knn_filter, knn_index, KnnIndex
 from . import utils
 from . import metric
 from .module.loss import geodesic_loss

@@ -203,20 +203,7 @@ nbr_finish_kernel(NbrFinishArgs<T> a) {
   }
 }
 
-// ---- voxel keys
-// minimum over the 64 lanes, valid in lane 63: wave_prefix_add's seven DPP steps with min for + and +inf for 0
-template <class T> __device__ __forceinline__ T wave_min63(T v) {
-  const T v0 = v, z = knn_inf<T>();
-  v = knn_min(dpp_mov<DPP_ROW_SHR1, 0xf, 0xf>(z, v0), v);
-  v = knn_min(dpp_mov<DPP_ROW_SHR2, 0xf, 0xf>(z, v0), v);
-  v = knn_min(dpp_mov<DPP_ROW_SHR3, 0xf, 0xf>(z, v0), v);
-  v = knn_min(dpp_mov<DPP_ROW_SHR4, 0xf, 0xe>(z, v), v);
-  v = knn_min(dpp_mov<DPP_ROW_SHR8, 0xf, 0xc>(z, v), v);
-  v = knn_min(dpp_mov<DPP_ROW_BCAST15, 0xa, 0xf>(z, v), v);
-  v = knn_min(dpp_mov<DPP_ROW_BCAST31, 0xc, 0xf>(z, v), v);
-  return v;
-}
-
+// ---- voxel keys (wave_min63: knn_tile.h)
 // the three column minima over the workgroup's lanes, left in mn[0..2] (every lane calls it; a barrier follows inside)
 template <class T> __device__ __forceinline__ void block_min3(const T* m, T (*red)[3], T* mn) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -39,6 +39,39 @@ template <class T, int K> __device__ __forceinline__ void knn_insert(T* d, int* 
   }
 }
 
+// the same for candidates that do not arrive in ascending index (knn_grid.hip): the list is ordered by (d^2, index), which is the
+// order the ascending visit with a strict < leaves.  The caller has checked (c, ci) < (d[K-1], id[K-1]).
+template <class T> __device__ __forceinline__ bool knn_before(T c, int ci, T d, int id) { return c < d || (c == d && ci < id); }
+template <class T, int K> __device__ __forceinline__ void knn_insert_lex(T* d, int* id, T c, int ci) {
+#pragma unroll
+  for (int i = K - 1; i > 0; --i) {
+    if (knn_before(c, ci, d[i - 1], id[i - 1])) {
+      d[i] = d[i - 1];
+      id[i] = id[i - 1];
+    } else if (knn_before(c, ci, d[i], id[i])) {
+      d[i] = c;
+      id[i] = ci;
+    }
+  }
+  if (knn_before(c, ci, d[0], id[0])) {
+    d[0] = c;
+    id[0] = ci;
+  }
+}
+
+// minimum over the 64 lanes, valid in lane 63: wave_prefix_add's seven DPP steps with min for + and +inf for 0
+template <class T> __device__ __forceinline__ T wave_min63(T v) {
+  const T v0 = v, z = knn_inf<T>();
+  v = knn_min(dpp_mov<DPP_ROW_SHR1, 0xf, 0xf>(z, v0), v);
+  v = knn_min(dpp_mov<DPP_ROW_SHR2, 0xf, 0xf>(z, v0), v);
+  v = knn_min(dpp_mov<DPP_ROW_SHR3, 0xf, 0xf>(z, v0), v);
+  v = knn_min(dpp_mov<DPP_ROW_SHR4, 0xf, 0xe>(z, v), v);
+  v = knn_min(dpp_mov<DPP_ROW_SHR8, 0xf, 0xc>(z, v), v);
+  v = knn_min(dpp_mov<DPP_ROW_BCAST15, 0xa, 0xf>(z, v), v);
+  v = knn_min(dpp_mov<DPP_ROW_BCAST31, 0xc, 0xf>(z, v), v);
+  return v;
+}
+
 // ---- a tile of `nbr` from HBM to the three LDS planes
 // full && vec: the slab of kKnnTile rows as 16-byte loads, held in registers (knn_fetch) until the previous tile is done with
 // (knn_commit).  Otherwise element by element (the ragged last tile of the cloud, or a base that is not 16-byte aligned), with

@@ -14,7 +14,8 @@ the blocks for intrinsics, pose and point, ``pplie_bal_vjp`` contracts all three
 
 ``knn`` (reference geometry.py:228-313) streams the neighbour cloud through LDS and keeps every reference point's best k in
 registers (csrc/knn.hip): the ``[N1, N2]`` distance matrix of the reference formulation is never formed.  ``_icp_stats`` is the
-same pass with the sums one ICP iteration needs (module/icp.py).
+same pass with the sums one ICP iteration needs (module/icp.py).  ``knn_index`` builds a uniform grid over a neighbour cloud once
+(csrc/knn_grid.hip); ``knn(ref, index)`` then searches only the cells around every query, with the same results bit for bit.
 
 ``nbr_filter`` / ``knn_filter`` / ``voxel_filter`` (reference geometry.py:436-664) are the steps before registration
 (csrc/cloud_filter.hip): the cloud streamed against itself with a count under the radius kept next to the best-k list, and voxel
@@ -371,13 +372,14 @@ def _knn_flat(t, batch):
     return t.expand(batch + (n, 3)).reshape(-1, n, 3).contiguous(), n
 
 
-def _knn_launch(ref, rs, nbr, ns, B, k, T=None, splits=None, stats=None):
+def _knn_launch(ref, rs, nbr, ns, B, k, T=None, splits=None, stats=None, grid=None):
     """partial pass (+ merge pass) on flattened clouds.  Returns (values, indices) ``[B, N1, k]``, or with ``stats`` (a dict
-    that keeps the scratch of an ICP loop between iterations) the 16 fp64 sums ``[B, 16]`` of the k = 1 correspondences."""
+    that keeps the scratch of an ICP loop between iterations) the 16 fp64 sums ``[B, 16]`` of the k = 1 correspondences.
+    With ``grid = (KnnIndex of nbr, query order or None)`` the partial lists come from the grid query (one split)."""
     N1, N2, dev, dt = ref.shape[-2], nbr.shape[-2], ref.device, ref.dtype
     nt = -(-N2 // _KNN_TILE)
     S = splits if splits is not None else -(-512 // (B * -(-N1 // _KNN_BLOCK)))       # about two workgroups per CU
-    S = max(1, min(S, nt))
+    S = 1 if grid is not None else max(1, min(S, nt))
     lib, sfx = _C.library(), _C._SUFFIX[dt]
     partial = lib.symbol("pplie_knn_partial" + sfx, _KNN_PARTIAL_SIG)
     merge = lib.symbol("pplie_knn_merge" + sfx, _KNN_MERGE_SIG)
@@ -387,7 +389,7 @@ def _knn_launch(ref, rs, nbr, ns, B, k, T=None, splits=None, stats=None):
         if stats is None:
             values = torch.empty((B, N1, k), dtype=dt, device=dev)
             indices = torch.empty((B, N1, k), dtype=torch.int64, device=dev)
-            if S == 1:
+            if S == 1 and grid is None:
                 _C.check(partial(ref.data_ptr(), nbr.data_ptr(), tp, None, None, values.data_ptr(), indices.data_ptr(), B, N1, N2, k, 1,
                                  rs, ns, st), "pplie_knn_partial" + sfx)
                 return values, indices
@@ -402,8 +404,15 @@ def _knn_launch(ref, rs, nbr, ns, B, k, T=None, splits=None, stats=None):
                 stats.update(ws)
         else:
             ws = stats
-        _C.check(partial(ref.data_ptr(), nbr.data_ptr(), tp, ws["pd2"].data_ptr(), ws["pidx"].data_ptr(), None, None, B, N1, N2, k, S,
-                         rs, ns, st), "pplie_knn_partial" + sfx)
+        if grid is None:
+            _C.check(partial(ref.data_ptr(), nbr.data_ptr(), tp, ws["pd2"].data_ptr(), ws["pidx"].data_ptr(), None, None, B, N1, N2, k, S,
+                             rs, ns, st), "pplie_knn_partial" + sfx)
+        else:
+            index, order = grid
+            _C.check(lib.symbol("pplie_knn_grid" + sfx, _GRID_QUERY_SIG)(
+                ref.data_ptr(), tp, None if order is None else order.data_ptr(), index.planes.data_ptr(), index.oidx.data_ptr(),
+                index.starts.data_ptr(), index.header.data_ptr(), index.cbase.data_ptr(), ws["pd2"].data_ptr(), ws["pidx"].data_ptr(),
+                B, N1, index.planes.shape[1], k, rs, rs, 1 if ns else 0, st), "pplie_knn_grid" + sfx)
         if stats is None:
             _C.check(merge(ws["pd2"].data_ptr(), ws["pidx"].data_ptr(), values.data_ptr(), indices.data_ptr(), None, None, None, None,
                            None, None, B, N1, N2, k, S, rs, ns, st), "pplie_knn_merge" + sfx)
@@ -414,10 +423,104 @@ def _knn_launch(ref, rs, nbr, ns, B, k, T=None, splits=None, stats=None):
         return sums
 
 
-def _icp_stats(source, ss, target, ts, T, B, ws, splits=None):
+def _icp_stats(source, ss, target, ts, T, B, ws, splits=None, grid=None):
     """per batch element, over the nearest target point q of every p = T . source: ``[sum d, sum p (3), sum q (3),
-    sum q p^T (9)]`` in fp64 ``[B, 16]`` -- two launches, the moved cloud is never written"""
-    return _knn_launch(source, ss, target, ts, B, 1, T=T, splits=splits, stats=ws)
+    sum q p^T (9)]`` in fp64 ``[B, 16]`` -- two launches, the moved cloud is never written.  ``grid``: (the target's KnnIndex,
+    the order of the source or None) searches the index instead of the whole target."""
+    return _knn_launch(source, ss, target, ts, B, 1, T=T, splits=splits, stats=ws, grid=grid)
+
+
+# ---- exact nearest neighbours through a uniform grid over the neighbour cloud (csrc/knn_grid.hip)
+_GRID_OCCUPANCY = 8.0         # mean points per cell of the bounding box (swept 4 / 8 / 16, DESIGN.md section 3.9)
+_GRID_ORDER_OCCUPANCY = 256.0  # ... of the coarse grid the queries are ordered by: about one workgroup per cell
+_GRID_MAX_CELLS = 1 << 24
+_GRID_KNN_MIN = (1_000_000, 1_000_000)   # (N1, N2) from which pp.knn(ref, tensor) builds an index itself (measured, section 3.9)
+_GRID_ICP_MIN_N2 = None       # N2 from which ICP builds the index of its target; None: off (the grid lost at 1e4 x 1e5)
+_GRID_BBOX_SIG = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double] + [ctypes.c_void_p] * 3
+_GRID_KEYS_SIG = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4
+_GRID_TABLES_SIG = [ctypes.c_void_p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_void_p] * 4
+_GRID_QUERY_SIG = [ctypes.c_void_p] * 10 + [ctypes.c_int64] * 3 + [ctypes.c_int] + [ctypes.c_int64] * 2 + [ctypes.c_int, ctypes.c_void_p]
+
+
+def _grid_keys(flat, occupancy, cells=None):
+    """header ``[B, 8]`` (fp64: min, h, gx, gy, gz, non-finite flag) and int32 cell keys ``[B * N]`` of ``flat [B, N, 3]``.
+    ``cells(header)`` returns the first cell of every batch element (int32 ``[B]``, on the device); without it the elements
+    are 2^21 cells apart."""
+    B, N = flat.shape[:2]
+    dev, lib, sfx = flat.device, _C.library(), _C._SUFFIX[flat.dtype]
+    part = torch.empty((B, min(256, -(-N // 256)), 7), dtype=flat.dtype, device=dev)
+    header = torch.empty((B, 8), dtype=torch.float64, device=dev)
+    keys = torch.empty(B * N, dtype=torch.int32, device=dev)
+    st = _C.stream_ptr(dev)
+    _C.check(lib.symbol("pplie_knn_grid_bbox" + sfx, _GRID_BBOX_SIG)(flat.data_ptr(), B, N, occupancy, part.data_ptr(), header.data_ptr(),
+                                                                     st), "pplie_knn_grid_bbox" + sfx)
+    cbase = None if cells is None else cells(header)
+    _C.check(lib.symbol("pplie_knn_grid_keys" + sfx, _GRID_KEYS_SIG)(flat.data_ptr(), B, N, header.data_ptr(),
+                                                                     None if cbase is None else cbase.data_ptr(), keys.data_ptr(), st),
+             "pplie_knn_grid_keys" + sfx)
+    return header, cbase, keys
+
+
+def _grid_order(flat):
+    """the order in which the grid query takes the points of ``flat [B, N, 3]`` (a locality hint: neighbours in the list are
+    neighbours in space, so a workgroup's 256 queries share a small cell box), or None where it would not help"""
+    if flat.shape[1] <= _KNN_BLOCK or flat.shape[0] > 1023:
+        return None
+    with _C._on_device(flat.device):
+        return torch.sort(_grid_keys(flat, _GRID_ORDER_OCCUPANCY)[2], stable=True).indices
+
+
+class KnnIndex:
+    """A uniform grid over the cloud ``nbr (..., N2, 3)`` for :func:`knn`: the cloud sorted by cell as three planes, the
+    permutation back to the original indices and the table of cell starts (csrc/knn_grid.hip).  Built once by
+    :func:`knn_index`, searched many times; the results are the brute-force route's bit for bit."""
+
+    def __init__(self, nbr, occupancy=_GRID_OCCUPANCY):
+        why = None
+        if not (isinstance(nbr, torch.Tensor) and nbr.is_cuda and _C._test_backend is None):
+            why = "the cloud is not on a HIP device"
+        elif nbr.dtype not in _C._SUFFIX:
+            why = f"dtype {nbr.dtype} (float32 / float64 only)"
+        elif nbr.dim() < 2 or nbr.shape[-1] != 3:
+            why = f"shape {tuple(nbr.shape)} (the points must be 3-D: (..., N2, 3))"
+        elif nbr.numel() == 0:
+            why = "the cloud is empty"
+        elif nbr.shape[:-2].numel() > 65535 or nbr.numel() // 3 > 2 ** 30:
+            why = "more than 65535 clouds or 2^30 points"
+        if why is not None:
+            raise ValueError("pypose_amd: knn_index: " + why)
+        self.cloud, self.batch, self.n2, self.occupancy = nbr, nbr.shape[:-2], nbr.shape[-2], float(occupancy)
+        B, N = self.batch.numel(), self.n2
+        flat = nbr.detach().reshape(B, N, 3).contiguous()
+        self.flat, self.ns = (flat[0], 0) if B == 1 else (flat, N)        # as _knn_flat gives a cloud
+        dev, sfx = nbr.device, _C._SUFFIX[nbr.dtype]
+
+        def cells(header):                                                # the one host read: sizes and flags
+            host = header.cpu()
+            if host[:, 7].any():
+                raise ValueError("pypose_amd: knn_index: the cloud has non-finite points")
+            count = host[:, 4:7].prod(dim=1).to(torch.int64)
+            self.cells = int(count.sum())
+            if self.cells > _GRID_MAX_CELLS:
+                raise ValueError(f"pypose_amd: knn_index: {self.cells} cells for {B} clouds (at most 2^24)")
+            return (torch.cumsum(count, 0) - count).to(torch.int32).to(dev)
+
+        with _C._on_device(dev):
+            self.header, self.cbase, keys = _grid_keys(flat, self.occupancy, cells)
+            keys, perm = torch.sort(keys, stable=True)
+            self.planes = torch.empty((3, B * N), dtype=nbr.dtype, device=dev)
+            self.oidx = torch.empty(B * N, dtype=torch.int32, device=dev)
+            self.starts = torch.empty(self.cells + 1, dtype=torch.int32, device=dev)
+            _C.check(_C.library().symbol("pplie_knn_grid_tables" + sfx, _GRID_TABLES_SIG)(
+                flat.data_ptr(), keys.data_ptr(), perm.data_ptr(), B, N, self.cells, self.planes.data_ptr(), self.oidx.data_ptr(),
+                self.starts.data_ptr(), _C.stream_ptr(dev)), "pplie_knn_grid_tables" + sfx)
+
+
+def knn_index(nbr, _occupancy=_GRID_OCCUPANCY):
+    """The :class:`KnnIndex` of ``nbr (..., N2, 3)``, to be passed to :func:`knn` in the place of the cloud.  Raises
+    ``ValueError`` with the reason for anything the grid kernels do not take: a cloud that is not on a HIP device, not float32 /
+    float64, not 3-D, empty, with non-finite points, or a batch whose grids need more than 2^24 cells."""
+    return KnnIndex(nbr, _occupancy)
 
 
 def _knn_tensor(ref, nbr, k, ord, dim, largest, sorted):
@@ -434,7 +537,7 @@ def _knn_tensor(ref, nbr, k, ord, dim, largest, sorted):
     return torch.return_types.topk((torch.cat([p.values for p in parts], -2), torch.cat([p.indices for p in parts], -2)))
 
 
-def knn(ref, nbr, k=1, ord=2, dim=-1, largest=False, sorted=True, _splits=None):
+def knn(ref, nbr, k=1, ord=2, dim=-1, largest=False, sorted=True, _splits=None, _order=True):
     """The ``k`` nearest (``largest``: furthest) points of ``nbr (..., N2, D)`` for every point of ``ref (..., N1, D)`` in the
     ``ord``-norm: ``torch.return_types.topk(values, indices)``, both ``(..., N1, k)`` (reference geometry.py:228-313).
 
@@ -442,16 +545,34 @@ def knn(ref, nbr, k=1, ord=2, dim=-1, largest=False, sorted=True, _splits=None):
     neighbour cloud is streamed through LDS, every reference point keeps its best k in registers, and the ``[N1, N2]``
     distance matrix is never formed; equal distances go to the smaller index.  Everything else takes the tensor formulation.
     When a gradient is recorded the indices come from the kernels and the values are recomputed from the gathered
-    neighbours, which gives the reference's gradients in O(N1 k) work."""
+    neighbours, which gives the reference's gradients in O(N1 k) work.
+
+    ``nbr`` may be the :class:`KnnIndex` of the cloud (:func:`knn_index`): the search then visits only the cells around every
+    query (csrc/knn_grid.hip) and returns the same values and indices, bit for bit.  What the kernels do not take falls back
+    to the index's cloud."""
+    index = nbr if isinstance(nbr, KnnIndex) else None
+    if index is not None:
+        nbr = index.cloud
     if not _knn_on_kernels(ref, nbr, k, ord, dim, largest):
         return _knn_tensor(ref, nbr, k, ord, dim, largest, sorted)
     n1, n2 = ref.shape[-2], nbr.shape[-2]
     if k > n2:
         raise RuntimeError("selected index k out of range")
     batch = torch.broadcast_shapes(ref.shape[:-2], nbr.shape[:-2])
+    if index is None and _GRID_KNN_MIN is not None and n1 >= _GRID_KNN_MIN[0] and n2 >= _GRID_KNN_MIN[1]:
+        try:
+            index = KnnIndex(nbr)
+        except ValueError:                                                            # (non-finite points, the cell cap)
+            pass
+    if index is not None and index.batch.numel() not in (1, batch.numel()):           # a partly broadcast batch of indices
+        index = None
     r, rs = _knn_flat(ref.detach(), batch)
-    n, ns = _knn_flat(nbr.detach(), batch)
-    values, indices = _knn_launch(r, rs, n, ns, batch.numel(), k, splits=_splits)
+    if index is None:
+        n, ns = _knn_flat(nbr.detach(), batch)
+        values, indices = _knn_launch(r, rs, n, ns, batch.numel(), k, splits=_splits)
+    else:
+        order = _grid_order(r.view(-1, n1, 3)) if _order else None
+        values, indices = _knn_launch(r, rs, index.flat, index.ns, batch.numel(), k, grid=(index, order))
     values, indices = values.view(batch + (n1, k)), indices.view(batch + (n1, k))
     if torch.is_grad_enabled() and (ref.requires_grad or nbr.requires_grad):
         picked = torch.gather(nbr.expand(batch + (n2, 3)), -2, indices.reshape(batch + (n1 * k, 1)).expand(batch + (n1 * k, 3)))

@@ -3,8 +3,9 @@
 On the device (3-D clouds of one dtype, Euclidean distance) one iteration is two launches of csrc/knn.hip and a 3 x 3 SVD: the
 partial pass searches the target for every point of ``T . source`` with the cumulative transform ``T`` applied in registers
 (the moved cloud is never written), the merge pass leaves ``sum d, sum p, sum q, sum q p^T`` per batch element in fp64, and the
-Kabsch step (centroids, centred cross-covariance, SVD, the reflection rule of ``svdtf``) works on those 16 numbers.  Elsewhere
-the reference's loop runs over ``pp.knn`` / ``pp.svdtf``.
+Kabsch step (centroids, centred cross-covariance, SVD, the reflection rule of ``svdtf``) works on those 16 numbers.  Above
+``geometry._GRID_ICP_MIN_N2`` target points the search goes through a grid index of the target built once per ``forward``
+(csrc/knn_grid.hip): same matches, fewer pairs.  Elsewhere the reference's loop runs over ``pp.knn`` / ``pp.svdtf``.
 """
 import torch
 from torch import nn
@@ -56,10 +57,15 @@ class ICP(nn.Module):
             T = identity_SE3(B, dtype=source.dtype, device=source.device)
         else:
             T = SE3(init.tensor().expand(batch + (7,)).reshape(B, 7).contiguous())
-        ws = {}
+        ws, grid = {}, None
+        if _geo._GRID_ICP_MIN_N2 is not None and target.shape[-2] >= _geo._GRID_ICP_MIN_N2:
+            try:        # the target does not move: one index for the whole loop; a rigid motion keeps a compact tile of the source compact
+                grid = (_geo.KnnIndex(tgt), _geo._grid_order(src.view(-1, n, 3)))
+            except ValueError:                                                        # (non-finite points, the cell cap)
+                pass
         self.stepper.reset()
         while self.stepper.continual():
-            sums = _geo._icp_stats(src, ss, tgt, ts, T.tensor(), B, ws)
+            sums = _geo._icp_stats(src, ss, tgt, ts, T.tensor(), B, ws, grid=grid)
             error = (sums[:, 0] / n).to(source.dtype).view(batch)
             p, q = sums[:, 1:4] / n, sums[:, 4:7] / n
             U, _, Vh = torch.linalg.svd(sums[:, 7:].view(B, 3, 3) - n * q.unsqueeze(-1) * p.unsqueeze(-2))
