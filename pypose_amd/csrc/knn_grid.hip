@@ -32,24 +32,13 @@
 // full, for the box grown by half its size on each side), the workgroup takes the union, at least the old box grown by one cell
 // (so the loop ends after at most 128 passes, at the whole grid), the open lanes reset their lists and rescan; closed lanes take
 // no insertions.  Correctness does not depend on how the queries are ordered: a scattered tile degenerates to brute force.
-#include <climits>
-
-#include "knn_tile.h"
+// (The cell arithmetic, the box union, the run table and the stream loaders live in knn_grid_box.h, shared with nbr_grid.hip.)
+#include "knn_grid_box.h"
 
 namespace pplie {
 
-constexpr int kGridBlock = 256;
-constexpr int kGridMaxAxis = 128;    // cells per axis
 constexpr int kGridParts = 256;      // workgroups per batch element of the bounding-box launch
-constexpr int kGridRuns = 256;       // runs of the box in LDS at a time
-constexpr int kGridHdr = 8;          // doubles per header: min (3), h, gx, gy, gz, non-finite flag
 constexpr int kGridRed = 7;          // min p (3), min -p (3), min -bad
-
-// cell of the offset coordinate rel = p - min on an axis of g cells; anything below the grid (and a NaN) goes to cell 0
-template <class T> __device__ __forceinline__ int grid_cell(T rel, T h, int g) {
-  const T q = rel / h;
-  return !(q > T(0)) ? 0 : q >= T(g) ? g - 1 : (int)q;
-}
 
 // the kGridRed minima over the workgroup's lanes, in red[0][.] after the call (every lane calls it; barriers inside)
 template <class T> __device__ __forceinline__ void grid_block_min(const T* m, T (*red)[kGridRed]) {
@@ -126,19 +115,6 @@ grid_header_kernel(const T* __restrict__ part, int P, int64_t N, double occ, dou
   H[7] = red[0][6] < T(0) ? 1.0 : 0.0;
 }
 
-template <class T> struct GridHeader {
-  T mn[3], h;
-  int g[3];
-  __device__ __forceinline__ explicit GridHeader(const double* H) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      mn[c] = (T)H[c];
-      g[c] = (int)H[4 + c];
-    }
-    h = (T)H[3];
-  }
-};
-
 // cbase: first cell of every batch element in the cell table, or NULL: 2^21 = 128^3 cells apart (a key to sort by, no table)
 template <class T>
 __global__ void __launch_bounds__(kGridBlock)
@@ -190,11 +166,6 @@ template <class T> struct KnnGridArgs {
   int k, idx_bstride;                                    // 0: one index for the whole batch, 1: one per batch element
 };
 
-template <class T> struct GridFetch {
-  T x[4], y[4], z[4];
-  int id[4];
-};
-
 template <class T, int K>
 __global__ void __launch_bounds__(kKnnBlock)
 knn_grid_kernel(KnnGridArgs<T> a) {
@@ -205,7 +176,7 @@ knn_grid_kernel(KnnGridArgs<T> a) {
   __shared__ float red[kKnnBlock / 64][6];
   __shared__ int sbox[6];
   __shared__ double wsum[kKnnBlock / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t b = blockIdx.y, slot = (int64_t)blockIdx.x * kKnnBlock + tid;
   const bool act = slot < a.N1;
   const int64_t row = !act ? 0 : a.qperm ? a.qperm[b * a.perm_bstride + slot] - b * a.perm_bstride : slot;
@@ -250,33 +221,7 @@ knn_grid_kernel(KnnGridArgs<T> a) {
 
   for (;;) {
     // ---- the box: union of the open lanes' wishes and of the previous box grown by a cell, clamped to the grid
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-      const float w = !open ? knn_inf<float>() : c < 3 ? (float)lo[c] : (float)-hi[c - 3];      // |cells| <= 129: exact
-      const float t = wave_min63<float>(w);
-      if (lane == 63) red[wave][c] = t;
-    }
-    __syncthreads();
-    if (tid < 6) {
-      const int c = tid < 3 ? tid : tid - 3, top = (c == 0 ? G.g[0] : c == 1 ? G.g[1] : G.g[2]) - 1;
-      const int prev = sbox[tid];                        // (the previous box; not read on the first pass)
-      const float m = knn_min(knn_min(red[0][tid], red[1][tid]), knn_min(red[2][tid], red[3][tid]));     // (some lane is open)
-      int v = tid < 3 ? (int)m : (int)-m;
-      if (tid < 3) {
-        if (!first && v > prev - 1) v = prev - 1;
-        v = v < 0 ? 0 : v;
-      } else {
-        if (!first && v < prev + 1) v = prev + 1;
-        v = v > top ? top : v;
-      }
-      sbox[tid] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      blo[c] = sbox[c];
-      bhi[c] = sbox[3 + c];
-    }
+    grid_box_union(open, lo, hi, G.g, first, red, sbox, blo, bhi);
     first = false;
     const bool whole = blo[0] == 0 && blo[1] == 0 && blo[2] == 0 && bhi[0] == G.g[0] - 1 && bhi[1] == G.g[1] - 1 && bhi[2] == G.g[2] - 1;
 
@@ -284,68 +229,18 @@ knn_grid_kernel(KnnGridArgs<T> a) {
     const int by = bhi[1] - blo[1] + 1, nruns = by * (bhi[2] - blo[2] + 1);
     for (int r0 = 0; r0 < nruns; r0 += kGridRuns) {
       const int nr = nruns - r0 < kGridRuns ? nruns - r0 : kGridRuns;
-      int len = 0;
-      if (tid < nr) {
-        const int r = r0 + tid, zz = blo[2] + r / by, yy = blo[1] + r % by, c0 = cb + (zz * G.g[1] + yy) * G.g[0];
-        const int s = a.starts[c0 + blo[0]];
-        rbeg[tid] = s;
-        len = a.starts[c0 + bhi[0] + 1] - s;
-      }
-      const double inc = wave_prefix_add<double>((double)len);        // (integers below 2^31: exact)
-      if (lane == 63) wsum[wave] = inc;
-      __syncthreads();
-      double off = 0.0;
-      for (int u = 0; u < wave; ++u) off += wsum[u];
-      if (tid < nr) rpre[tid] = (int)(off + inc) - len;               // stream position of the run's first point
-      const int total = (int)(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
-      __syncthreads();
-
-      // stream position -> sorted position: the last run that starts at or before it (runs of length 0 are stepped over)
-      auto fetch = [&](int t, GridFetch<T>& f) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int v = t * kKnnTile + i * kKnnBlock + tid;
-          f.x[i] = knn_inf<T>();
-          f.y[i] = T(0);
-          f.z[i] = T(0);
-          f.id[i] = INT_MAX;
-          if (v < total) {
-            int r = 0;
-#pragma unroll
-            for (int step = kGridRuns / 2; step > 0; step >>= 1) {
-              const int c = r + step;
-              if (c < nr && rpre[c] <= v) r = c;
-            }
-            const int src = rbeg[r] + (v - rpre[r]);
-            f.x[i] = gx[src];
-            f.y[i] = gy[src];
-            f.z[i] = gz[src];
-            f.id[i] = a.oidx[src];
-          }
-        }
-      };
-      auto commit = [&](const GridFetch<T>& f, int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int v = i * kKnnBlock + tid;
-          lds[buf][v] = f.x[i];
-          lds[buf][kKnnTile + v] = f.y[i];
-          lds[buf][2 * kKnnTile + v] = f.z[i];
-          lid[buf][v] = f.id[i];
-        }
-      };
-
+      const int total = grid_run_table(a.starts, cb, G.g, blo, bhi, by, r0, nr, rbeg, rpre, wsum);
       const int ntiles = (total + kKnnTile - 1) / kKnnTile;
-      GridFetch<T> f;
+      GridFetch<T, true> f;
       if (ntiles > 0) {
-        fetch(0, f);
-        commit(f, 0);
+        grid_fetch<T, true>(0, total, nr, rbeg, rpre, gx, gy, gz, a.oidx, f);
+        grid_commit<T, true>(f, lds[0], lid[0]);
       }
       __syncthreads();
       for (int t = 0; t < ntiles; ++t) {
         const int cur = t & 1;
         const bool next = t + 1 < ntiles;
-        if (next) fetch(t + 1, f);                       // in flight while this tile is computed on
+        if (next) grid_fetch<T, true>(t + 1, total, nr, rbeg, rpre, gx, gy, gz, a.oidx, f);                       // in flight while this tile is computed on
 
         const T* sx = lds[cur];
         const T* sy = sx + kKnnTile;
@@ -375,7 +270,7 @@ knn_grid_kernel(KnnGridArgs<T> a) {
           }
         }
 
-        if (next) commit(f, cur ^ 1);
+        if (next) grid_commit<T, true>(f, lds[cur ^ 1], lid[cur ^ 1]);
         __syncthreads();                                 // the other buffer is complete; every lane is done reading this one
       }
       __syncthreads();                                   // ... and with the run table

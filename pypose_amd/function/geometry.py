@@ -19,7 +19,8 @@ same pass with the sums one ICP iteration needs (module/icp.py).  ``knn_index`` 
 
 ``nbr_filter`` / ``knn_filter`` / ``voxel_filter`` (reference geometry.py:436-664) are the steps before registration
 (csrc/cloud_filter.hip): the cloud streamed against itself with a count under the radius kept next to the best-k list, and voxel
-keys plus a segmented mean over the sorted keys.  ``random_filter`` is an index.
+keys plus a segmented mean over the sorted keys; on large clouds the two neighbour filters search through the grid index instead
+(csrc/nbr_grid.hip: only the cells within the radius).  ``random_filter`` is an index.
 """
 import ctypes
 import math
@@ -436,7 +437,12 @@ _GRID_ORDER_OCCUPANCY = 256.0  # ... of the coarse grid the queries are ordered 
 _GRID_MAX_CELLS = 1 << 24
 _GRID_KNN_MIN = (1_000_000, 1_000_000)   # (N1, N2) from which pp.knn(ref, tensor) builds an index itself (measured, section 3.9)
 _GRID_ICP_MIN_N2 = None       # N2 from which ICP builds the index of its target; None: off (the grid lost at 1e4 x 1e5)
-_GRID_BBOX_SIG = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double] + [ctypes.c_void_p] * 3
+# N from which nbr_filter (count only) / knn_filter (lists) build an index of the cloud themselves, unless the radius's cell box
+# is estimated to hold more than the share of the cloud below (_filter_index; measured); None: off
+_GRID_FILTER_MIN_N = (100_000, 1_000_000)
+_GRID_FILTER_BOX_SHARE = 1 / 128
+_NBR_GRID_SIG = [ctypes.c_void_p] * 6 + [ctypes.c_double, ctypes.c_int] + [ctypes.c_int64] * 2 + [ctypes.c_void_p]
+_GRID_BBOX_SIG =[ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double] + [ctypes.c_void_p] * 3
 _GRID_KEYS_SIG = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_void_p] * 4
 _GRID_TABLES_SIG = [ctypes.c_void_p] * 3 + [ctypes.c_int64] * 3 + [ctypes.c_void_p] * 4
 _GRID_QUERY_SIG = [ctypes.c_void_p] * 10 + [ctypes.c_int64] * 3 + [ctypes.c_int] + [ctypes.c_int64] * 2 + [ctypes.c_int, ctypes.c_void_p]
@@ -496,7 +502,7 @@ class KnnIndex:
         dev, sfx = nbr.device, _C._SUFFIX[nbr.dtype]
 
         def cells(header):                                                # the one host read: sizes and flags
-            host = header.cpu()
+            host = self.header_host = header.cpu()
             if host[:, 7].any():
                 raise ValueError("pypose_amd: knn_index: the cloud has non-finite points")
             count = host[:, 4:7].prod(dim=1).to(torch.int64)
@@ -507,7 +513,8 @@ class KnnIndex:
 
         with _C._on_device(dev):
             self.header, self.cbase, keys = _grid_keys(flat, self.occupancy, cells)
-            keys, perm = torch.sort(keys, stable=True)
+            keys, self.perm = torch.sort(keys, stable=True)                 # (kept: the cloud's own order as queries, nbr_grid)
+            perm = self.perm
             self.planes = torch.empty((3, B * N), dtype=nbr.dtype, device=dev)
             self.oidx = torch.empty(B * N, dtype=torch.int32, device=dev)
             self.starts = torch.empty(self.cells + 1, dtype=torch.int32, device=dev)
@@ -605,27 +612,75 @@ def _radius2(radius, dtype):
     return r2 if radius >= 0 and r2 != float("inf") and r2 == r2 else None
 
 
-def _nbr_launch(points, r2, kk, nbr, splits=None):
+def _filter_index(xyz, r2, kk, grid):
+    """the :class:`KnnIndex` through which the neighbour filters search ``xyz [B, N, 3]``, or None for the brute-force route.
+    ``grid``: a KnnIndex of these columns (used), True (built; None where the index refuses the cloud), False, or None:
+    built from ``_GRID_FILTER_MIN_N[kk > 0]`` points, and used unless the cell box of the radius covers so much of the grid that the
+    estimated pairs per query -- the occupancy times the box's cells -- exceed ``_GRID_FILTER_BOX_SHARE * N``.  No host read
+    beyond the index's own."""
+    B, N = xyz.shape[:2]
+    if isinstance(grid, KnnIndex):
+        if (grid.batch.numel(), grid.n2, grid.cloud.dtype, grid.cloud.device) != (B, N, xyz.dtype, xyz.device):
+            raise ValueError("pypose_amd: _grid is not an index of this cloud's coordinate columns")
+        return grid
+    if grid is False or (grid is None and (_GRID_FILTER_MIN_N is None or N < _GRID_FILTER_MIN_N[kk > 0])):
+        return None
+    try:
+        index = KnnIndex(xyz)
+    except ValueError:                                                                # (non-finite points, the cell cap)
+        return None
+    if grid is None and r2 >= 0:
+        h, g = index.header_host[:, 3], index.header_host[:, 4:7]
+        reach = 2 * torch.ceil(math.sqrt(r2) / h) + 2                                 # cells per axis, a cell of slack
+        pairs = N / g.prod(dim=1) * torch.minimum(g, reach.unsqueeze(1)).prod(dim=1)
+        if pairs.max().item() > _GRID_FILTER_BOX_SHARE * N:
+            return None
+    return index
+
+
+def _nbr_counts_grid(index, r2, stop, B, N):
+    """int32 ``[B, 1, N]``: the points within ``sqrt(r2)`` of every point of the index's cloud (itself included), in original
+    order (csrc/nbr_grid.hip); a count is exact unless it exceeds ``stop``"""
+    dev, sfx = index.planes.device, _C._SUFFIX[index.planes.dtype]
+    pcount = torch.empty((B, 1, N), dtype=torch.int32, device=dev)
+    _C.check(_C.library().symbol("pplie_nbr_grid" + sfx, _NBR_GRID_SIG)(
+        index.planes.data_ptr(), index.oidx.data_ptr(), index.starts.data_ptr(), index.header.data_ptr(), index.cbase.data_ptr(),
+        pcount.data_ptr(), r2, stop, B, N, _C.stream_ptr(dev)), "pplie_nbr_grid" + sfx)
+    return pcount
+
+
+def _nbr_launch(points, r2, kk, nbr, splits=None, grid=None):
     """self-neighbourhood pass and finish on ``points [B, N, D]``: the keep mask ``[B, N]`` (count - 1 >= nbr) and, for
-    ``kk > 0``, the mean ``[B, N, D]`` over every point's kk nearest (itself among them)"""
+    ``kk > 0``, the mean ``[B, N, D]`` over every point's kk nearest (itself among them).  ``grid`` as :func:`_filter_index`
+    takes it: counts and lists then come from the grid kernels (one split each) and the finish is the same."""
     B, N, D = points.shape
     dev, dt = points.device, points.dtype
     cloud = points.contiguous()
     xyz = cloud if D == 3 else points[..., :3].contiguous()
-    S = splits if splits is not None else -(-512 // (B * -(-N // _KNN_BLOCK)))        # about two workgroups per CU
-    S = max(1, min(S, -(-N // _KNN_TILE)))
     lib, sfx = _C.library(), _C._SUFFIX[dt]
-    pcount = torch.empty((B, S, N), dtype=torch.int32, device=dev)
-    pd2 = torch.empty((B, S, N, kk), dtype=dt, device=dev) if kk else None
-    pidx = torch.empty((B, S, N, kk), dtype=torch.int32, device=dev) if kk else None
-    mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
-    mean = torch.empty((B, N, D), dtype=dt, device=dev) if kk else None
     ptr = lambda t: None if t is None else t.data_ptr()                               # noqa: E731
     nbr = max(-2 ** 31, min(math.ceil(nbr), 2 ** 31 - 1))                             # (counts are integers below 2^31)
     with _C._on_device(dev):
         st = _C.stream_ptr(dev)
-        _C.check(lib.symbol("pplie_nbr_partial" + sfx, _CF_PARTIAL_SIG)(xyz.data_ptr(), pcount.data_ptr(), ptr(pd2), ptr(pidx), B, N,
-                                                                        r2, kk, S, st), "pplie_nbr_partial" + sfx)
+        index = _filter_index(xyz, r2, kk, grid)
+        S = splits if splits is not None else -(-512 // (B * -(-N // _KNN_BLOCK)))    # about two workgroups per CU
+        S = 1 if index is not None else max(1, min(S, -(-N // _KNN_TILE)))
+        pd2 = torch.empty((B, S, N, kk), dtype=dt, device=dev) if kk else None
+        pidx = torch.empty((B, S, N, kk), dtype=torch.int32, device=dev) if kk else None
+        mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
+        mean = torch.empty((B, N, D), dtype=dt, device=dev) if kk else None
+        if index is None:
+            pcount = torch.empty((B, S, N), dtype=torch.int32, device=dev)
+            _C.check(lib.symbol("pplie_nbr_partial" + sfx, _CF_PARTIAL_SIG)(xyz.data_ptr(), pcount.data_ptr(), ptr(pd2), ptr(pidx), B, N,
+                                                                            r2, kk, S, st), "pplie_nbr_partial" + sfx)
+        else:
+            # (without a radius nothing reads the mask: no count launch, as r2 = -1 counts nothing on the brute-force route)
+            pcount = _nbr_counts_grid(index, r2, nbr, B, N) if r2 >= 0 else torch.zeros((B, 1, N), dtype=torch.int32, device=dev)
+            if kk:                                   # the cloud against its own index, in the index's own order
+                _C.check(lib.symbol("pplie_knn_grid" + sfx, _GRID_QUERY_SIG)(
+                    index.flat.data_ptr(), None, index.perm.data_ptr(), index.planes.data_ptr(), index.oidx.data_ptr(),
+                    index.starts.data_ptr(), index.header.data_ptr(), index.cbase.data_ptr(), pd2.data_ptr(), pidx.data_ptr(),
+                    B, N, B * N, kk, index.ns, index.ns, 1 if index.ns else 0, st), "pplie_knn_grid" + sfx)
         _C.check(lib.symbol("pplie_nbr_finish" + sfx, _CF_FINISH_SIG)(pcount.data_ptr(), ptr(pd2), ptr(pidx), ptr(cloud if kk else None),
                                                                       mask.data_ptr(), ptr(mean), B, N, D, kk, S, nbr, st),
                  "pplie_nbr_finish" + sfx)
@@ -640,7 +695,7 @@ def _nbr_count_tensor(xyz, radius, ord):
                       for i in range(0, n, chunk)]) if n else xyz.new_zeros((0,), dtype=torch.int64)
 
 
-def nbr_filter(points, nbr, radius, pdim=None, ord=2, return_mask=False, _splits=None):
+def nbr_filter(points, nbr, radius, pdim=None, ord=2, return_mask=False, _splits=None, _grid=None):
     """Drop the points of ``points (N, D)`` that have fewer than ``nbr`` neighbours within ``radius`` (``ord``-norm over the first
     ``pdim`` columns, default all of them): the kept rows in input order and, with ``return_mask``, the mask ``(N,)`` (reference
     geometry.py:436-493).  Point i is kept when ``#{j : d(i, j) <= radius} - 1 >= nbr``, the count including i itself.
@@ -648,13 +703,17 @@ def nbr_filter(points, nbr, radius, pdim=None, ord=2, return_mask=False, _splits
     HIP clouds (fp32 / fp64) with ``pdim == 3``, ``ord == 2`` and ``3 <= D <= 8`` run in csrc/cloud_filter.hip: the cloud is
     streamed against itself through LDS and the ``[N, N]`` distance matrix is never formed.  The kernel compares
     ``d^2 <= r^2`` with ``r^2 = radius * radius`` rounded once in the cloud's dtype, which can differ from the reference's
-    ``sqrt(...) <= radius`` only for pairs within a few ulp of the radius.  Everything else takes the tensor formulation."""
+    ``sqrt(...) <= radius`` only for pairs within a few ulp of the radius.  Everything else takes the tensor formulation.
+
+    ``_grid``: search through a uniform grid over the coordinate columns (csrc/nbr_grid.hip: only the cells within the radius are
+    visited; the same mask) -- True builds a :class:`KnnIndex` of them, a KnnIndex of them is used, False never, None decides by
+    size (``_GRID_FILTER_MIN_N``).  A cloud the index refuses (non-finite points) takes the brute-force route."""
     assert len(points.shape) == 2, "The point cloud dimension has to be 2."
     pdim = points.size(-1) if pdim is None else pdim
     assert points.size(-1) >= pdim, "The last dim of points should not less than pdim."
     r2 = _radius2(radius, points.dtype) if _filter_on_kernels(points, pdim, ord) else None
     if r2 is not None:
-        mask = _nbr_launch(points.detach().unsqueeze(0), r2, 0, nbr, _splits)[0][0]
+        mask = _nbr_launch(points.detach().unsqueeze(0), r2, 0, nbr, _splits, _grid)[0][0]
     else:
         mask = _nbr_count_tensor(points[..., :pdim].detach(), radius, ord) - 1 >= nbr
     return (points[mask], mask) if return_mask else points[mask]
@@ -757,7 +816,7 @@ def _knn_mean_tensor(points, xyz, kk, ord):
     return picked.view(points.shape[:-1] + (kk, D)).mean(dim=-2)
 
 
-def knn_filter(points, k, pdim=None, radius=None, ord=2, _splits=None):
+def knn_filter(points, k, pdim=None, radius=None, ord=2, _splits=None, _grid=None):
     """Smooth ``points (..., N, D)``: every point becomes the mean, over all D columns, of itself and its ``k`` nearest
     neighbours (``ord``-norm over the first ``pdim`` columns); with ``radius`` (then ``points`` is ``(N, D)``) only the points
     with at least ``k`` neighbours within ``radius`` are kept, in input order (reference geometry.py:605-664).
@@ -770,7 +829,10 @@ def knn_filter(points, k, pdim=None, radius=None, ord=2, _splits=None):
     HIP clouds (fp32 / fp64) with ``pdim == 3``, ``ord == 2``, ``3 <= D <= 8`` and ``k + 1 <= 16`` run in csrc/cloud_filter.hip:
     one streaming pass over the pairs keeps the count under the radius (``d^2 <= r^2``, ``r^2 = radius * radius`` rounded once in
     the cloud's dtype) next to the best k + 1, and the means are accumulated in fp64.  Everything else, and a cloud that records
-    a gradient, takes the tensor formulation."""
+    a gradient, takes the tensor formulation.
+
+    ``_grid`` as in :func:`nbr_filter`: the count comes from csrc/nbr_grid.hip and the lists from the cloud's own index
+    (csrc/knn_grid.hip), bit for bit the brute-force pass's, so the result is the same."""
     if radius is not None:
         assert len(points.shape) == 2, "The points dimension has to be 2 given radius."
     else:
@@ -783,7 +845,7 @@ def knn_filter(points, k, pdim=None, radius=None, ord=2, _splits=None):
     if k + 1 > n and n > 0:
         raise RuntimeError("selected index k out of range")
     if on_kernels and r2 is not None:
-        mask, mean = _nbr_launch(points.detach().reshape(-1, n, D), r2, k + 1, k, _splits)
+        mask, mean = _nbr_launch(points.detach().reshape(-1, n, D), r2, k + 1, k, _splits, _grid)
         return mean.view(points.shape) if radius is None else mean[0][mask[0]]
     xyz = points[..., :pdim]
     mean = _knn_mean_tensor(points, xyz, k + 1, ord)
